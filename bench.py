@@ -19,7 +19,9 @@ cannot see N devices.
 Prints ONE JSON line on rank 0 (contract in the task statement).  `value` is measured in the configuration of the
 drop-in block, gr::bluetooth::multi_sniffer::work (lib/multi_sniffer_impl.cc:107-149): classic search, LE pass,
 the symbols of every hit handed over with the GPU header sweep -- BTGPU_FLAG_LE | HEADERS (what host/blocks.cc
-sets).  Added objects: `roofline` (the step's dominant kernel: since round 6 exact_rows_kernel on the fp32 matrix
+sets).  A plain run sets up, warms up, times the K steps of that configuration and prints the line (`--dump-outputs DIR` also writes the
+records of the last timed step).  `--full` adds every other leg, each a run of its own after the headline's: `roofline` (the step's
+dominant kernel: since round 6 exact_rows_kernel on the fp32 matrix
 pipe), `roofline_bank` (the channel bank against the HBM roofline, rounds 1-5's `roofline`), `cpu_baseline`,
 `parity` (a differential of the records of one step against the CPU oracle run on all host cores over the first
 --parity-slots slots of the same capture, tests/paritylib.py), and at N = 1 `classic_only` (the same K steps
@@ -66,6 +68,11 @@ def parse_args(argv=None):
     ap.add_argument("--cfo-hz", type=float, default=75e3, help="carrier offset range of the bursts (SURVEY 8(d): +-75 kHz)")
     ap.add_argument("--max-payload-bits", type=int, default=2745, help="payload length range (SURVEY 8(d): 0-2745)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="after the headline region, every other leg and check too: roofline, cpu_baseline, parity, "
+                    "classic_only, c8, exact_all, verify A/B, host_fed (each with its own --no-... switch); without it the run is the headline alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the records the last timed step of the headline region handed to its "
+                    "caller as DIR/records.npy (float64 [n, 7]: slot, channel, kind, offset, lap, ac_errors, nsym; rows in ascending order) and "
+                    "DIR/snr_db.npy (float64 [n], the same rows)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="approximate budget of the single-thread cpu_baseline sample")
     ap.add_argument("--parity-slots", type=int, default=1600,
                     help="slots of the capture the all-core oracle differential covers (N = 1; 0 = skip)")
@@ -359,13 +366,22 @@ def run_rank(args):
             assert len(ints_u) * args.steps == len(ints), "steps produced different record sets"
             return bdist.sort_hits(ints_u, snr[idx])
         return ints, snr
-    ints, snr = one_copy(ints, snr)
+    if args.full or args.dump_outputs:
+        ints, snr = one_copy(ints, snr)
+    if args.dump_outputs and rank == 0:
+        # every step runs the same resident batch, so the one copy IS the last timed step's record set; harvest order is the device's,
+        # so the rows are put in ascending order of all seven fields: two builds can be compared row for row
+        order = np.lexsort(tuple(ints[:, c] for c in range(ints.shape[1] - 1, -1, -1))) if len(ints) else np.zeros(0, np.int64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "records.npy"), np.asarray(ints[order], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "snr_db.npy"), np.asarray(snr[order], dtype=np.float64))
+    full = args.full
 
     # ---- the drop-in block's configuration (N = 1): gr::bluetooth::multi_sniffer always runs the LE pass after the
     # classic one and hands the symbols of every hit to its packet handlers (lib/multi_sniffer_impl.cc:107-149), so
     # host/blocks.cc creates its handle with BTGPU_FLAG_LE | BTGPU_FLAG_HEADERS: the same K steps in that configuration
     # ---- A/B of the exact stage (N = 1): the same K steps with BTGPU_FLAG_NO_VERIFY -- what the confirmation of the records costs
-    if world == 1 and not args.no_ab and verify_obj["windows_per_step"] > 0:
+    if full and world == 1 and not args.no_ab and verify_obj["windows_per_step"] > 0:
         blk.close()
         blk = make_block(head_flags | pkg.FLAG_NO_VERIFY)
         a_el, a_ints, a_snr, _m, _f, _k1, _k2 = timed_region(blk, gather=False)
@@ -377,7 +393,7 @@ def run_rank(args):
 
     # ---- the classic-only configuration (N = 1): rounds 1-5's headline -- no LE pass, no symbol hand-over: the LAP list alone ----
     block_cfg = None
-    if world == 1 and not args.no_block_config and not args.classic_only:
+    if full and world == 1 and not args.no_block_config and not args.classic_only:
         blk.close()
         blk = make_block(0, timing=pkg.FLAG_TIMING)
         b_el, b_ints, b_snr, _m, _f, b_kms, b_kl = timed_region(blk, gather=False)
@@ -394,7 +410,7 @@ def run_rank(args):
 
     # ---- BASELINE configs[1] (N = 1): 8 channels at 8 Msps, the same flags, driver-timed ----
     c8 = None
-    if world == 1 and not args.no_c8 and args.workload == "c79":
+    if full and world == 1 and not args.no_c8 and args.workload == "c79":
         blk.close()
         w8 = WORKLOADS["c8"]
         S8 = 16384
@@ -449,7 +465,7 @@ def run_rank(args):
     # matrix pipe; every field of every record then equals the oracle's (nsym and the noise-born records included) ----
     exact_all = None
     x_ints = None
-    if world == 1 and not args.no_exact_all and not args.classic_only:
+    if full and world == 1 and not args.no_exact_all and not args.classic_only:
         blk.close()
         blk = make_block(head_flags | pkg.FLAG_EXACT_ALL)
         keep_steps, keep_warm = args.steps, args.warmup
@@ -468,7 +484,7 @@ def run_rank(args):
     # copied to the device as it lies; pageable: through the library's pinned staging buffers.  H2D alone = the same bytes with
     # hipMemcpyAsync from page-locked memory, the ceiling of this box's link.
     host_fed = None
-    if world == 1 and not args.no_host_fed:
+    if full and world == 1 and not args.no_host_fed:
         hb = 8
         seg_host = seg.cpu()
         pinned = seg_host.pin_memory()
@@ -509,22 +525,44 @@ def run_rank(args):
     total_samples = float(world) * S * slot * args.steps
     value = total_samples / elapsed / 1e6
 
-    # ---- correctness gate 1: ground-truth bursts reported (recall of the synthetic capture) ----
-    got = set((int(r[0]), int(r[1]), int(r[4])) for r in ints)           # (slot, channel, lap)
-    lo_slot, hi_slot = 0, world * S
-    if world > 1:                                   # a rank only knows its own truth; regenerate all
-        truth, _ = synth.burst_schedule(fs, fc, 0, world * S, laps, args.seed, args.occupancy, args.cfo_hz,
-                                        args.max_payload_bits)
-    expected = found = 0
-    for tr in truth:
-        det = tr["slot"] + 6                        # sniffer window lag: (history()-1)/slot = 6.3
-        if det + 1 >= hi_slot or tr["slot"] < lo_slot:
-            continue
-        expected += 1
-        if any((det + d, tr["channel"], tr["lap"]) in got for d in (-1, 0, 1)):
-            found += 1
+    out = {
+        "metric": "complex-IQ Msamples/s @ 79 ch" if args.workload == "c79" else "complex-IQ Msamples/s @ 8 ch",
+        "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": wl["name"], "sample_rate": fs, "center_freq": fc, "channels": nch,
+                   "slots_per_rank_per_step": S, "samples_per_rank_per_step": S * slot,
+                   "squelch_db": args.squelch, "burst_snr_db": args.snr, "piconets": args.piconets,
+                   "occupancy": args.occupancy, "cfo_hz": args.cfo_hz, "max_payload_bits": args.max_payload_bits,
+                   "mode": "multi_sniffer",
+                   "partition": "time x%d, halo %d + margin %d samples" % (world, H - 1, margin),
+                   "gather": ("one async all_gather_into_tensor per %d batches (%s, own stream), %d rounds" % (args.gather_every, args.backend, gatherer.rounds)) if gathering else "none",
+                   "flags": "ASYNC%s%s%s" % ("|LE" if args.le else "", "|HEADERS" if args.headers else "", ("|EXACT_PAYLOAD" if args.exact_payload else "") + ("" if args.no_timing else ("|TIMING" if args.full_timing else "|TIMING_BANK"))),
+                   "channelizer": {1: "direct", 2: "polyphase"}[int(des.channelizer)],
+                   "squelch_filter": {1: "direct", 2: "staged"}[int(des.squelch)]},
+        "ms_per_step_by_rank": [round(v / args.steps * 1e3, 3) for v in rank_elapsed],
+        "fence_ms": round(fence_ms, 3),
+        "step_enqueue_ms": [round(float(v), 3) for v in np.percentile(np.diff(np.array(marks)) * 1e3, [0, 50, 100])],
+    }
 
-    if rank == 0:
+    # ---- correctness gate 1: ground-truth bursts reported (recall of the synthetic capture) ----
+    expected = found = 0
+    if full:
+        got = set((int(r[0]), int(r[1]), int(r[4])) for r in ints)           # (slot, channel, lap)
+        lo_slot, hi_slot = 0, world * S
+        if world > 1:                                   # a rank only knows its own truth; regenerate all
+            truth, _ = synth.burst_schedule(fs, fc, 0, world * S, laps, args.seed, args.occupancy, args.cfo_hz,
+                                            args.max_payload_bits)
+        for tr in truth:
+            det = tr["slot"] + 6                        # sniffer window lag: (history()-1)/slot = 6.3
+            if det + 1 >= hi_slot or tr["slot"] < lo_slot:
+                continue
+            expected += 1
+            if any((det + d, tr["channel"], tr["lap"]) in got for d in (-1, 0, 1)):
+                found += 1
+
+    if full and rank == 0:
         # ---- roofline of the dominant kernel (HIP events inside libbtgpu, same stream) ----
         names = pkg.KERNEL_NAMES
         NK = len(names)
@@ -700,35 +738,18 @@ def run_rank(args):
                         parity["differential"]["other_only_gpu"] + parity["differential"]["other_only_ref"],
                         parity["differential"]["other_gpu"] + parity["differential"]["other_ref"])
 
-        out = {
-            "metric": "complex-IQ Msamples/s @ 79 ch" if args.workload == "c79" else "complex-IQ Msamples/s @ 8 ch",
-            "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": wl["name"], "sample_rate": fs, "center_freq": fc, "channels": nch,
-                       "slots_per_rank_per_step": S, "samples_per_rank_per_step": S * slot,
-                       "squelch_db": args.squelch, "burst_snr_db": args.snr, "piconets": args.piconets,
-                       "occupancy": args.occupancy, "cfo_hz": args.cfo_hz, "max_payload_bits": args.max_payload_bits,
-                       "mode": "multi_sniffer",
-                       "partition": "time x%d, halo %d + margin %d samples" % (world, H - 1, margin),
-                       "gather": ("one async all_gather_into_tensor per %d batches (%s, own stream), %d rounds" % (args.gather_every, args.backend, gatherer.rounds)) if gathering else "none",
-                       "flags": "ASYNC%s%s%s" % ("|LE" if args.le else "", "|HEADERS" if args.headers else "", ("|EXACT_PAYLOAD" if args.exact_payload else "") + ("" if args.no_timing else ("|TIMING" if args.full_timing else "|TIMING_BANK"))),
-                       "channelizer": {1: "direct", 2: "polyphase"}[int(des.channelizer)],
-                       "squelch_filter": {1: "direct", 2: "staged"}[int(des.squelch)]},
-            "ms_per_step_by_rank": [round(v / args.steps * 1e3, 3) for v in rank_elapsed],
+        out.update({
             "classic_only": block_cfg,
             "c8": c8,
             "exact_all": exact_all,
             "verify": verify_obj,
             "host_fed": host_fed,
-            "fence_ms": round(fence_ms, 3),
-            "step_enqueue_ms": [round(float(v), 3) for v in np.percentile(np.diff(np.array(marks)) * 1e3, [0, 50, 100])],
             "roofline": roof,
             "roofline_bank": roof_bank,
             "cpu_baseline": cpu,
             "parity": parity,
-        }
+        })
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1 or args.force_gather:
         dist.barrier()

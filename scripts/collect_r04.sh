@@ -16,7 +16,7 @@ if [ "${2:-tests}" = "tests" ]; then
   cp gpurun_out/cfo_curve_*.json "$OUT/" 2>/dev/null
 fi
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python $R/bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 KRE='_kernel'   # counters only on the library's kernels (all named *_kernel): rocprofv3 crashed inside torch's randn / mul_ launches of the C8 capture generator
 pmc() { # name slots bench-args...   -> $OUT/<name>_pmc_hbm.json, _pmc_sq.txt, _pmc_stall.txt, _kernel_stats.csv, _timeline.txt
   n=$1; slots=$2; shift; shift
@@ -37,13 +37,13 @@ pmc c79 2304
 pmc block 2304 --le --headers
 pmc c8 16384 --workload c8 --steps 100
 # the bench line again: picks the PMC summary up when it sits under profiles/ (here: passed explicitly)
-python $R/bench.py --no-cpu --no-block-config --no-ab --no-host-fed --pmc-json "$OUT/c79_pmc_hbm.json" > "$OUT/bench_with_traffic.json" 2>> "$OUT/bench.err"
+python $R/bench.py --full --no-cpu --no-block-config --no-ab --no-host-fed --pmc-json "$OUT/c79_pmc_hbm.json" > "$OUT/bench_with_traffic.json" 2>> "$OUT/bench.err"
 C8J=""; python -c "import json,sys; json.load(open(sys.argv[1]))" "$OUT/c8_pmc_hbm.json" 2>/dev/null && C8J="--pmc-json $OUT/c8_pmc_hbm.json"
-python $R/bench.py --workload c8 --steps 100 $C8J > "$OUT/c8_bench.json" 2> "$OUT/c8.err"
+python $R/bench.py --full --workload c8 --steps 100 $C8J > "$OUT/c8_bench.json" 2> "$OUT/c8.err"
 # N > 1 path on this one device: two ranks, time-partitioned, gathered (gloo), and the single-rank RCCL group
 cd $R
-python bench.py --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
-python bench.py --gpus 1 --force-gather --backend nccl --no-cpu --no-block-config --no-ab --no-host-fed 2> "$OUT/one_rank_rccl.err" | head -1 > "$OUT/one_rank_rccl_gather_bench.json"
+python bench.py --full --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
+python bench.py --full --gpus 1 --force-gather --backend nccl --no-cpu --no-block-config --no-ab --no-host-fed 2> "$OUT/one_rank_rccl.err" | head -1 > "$OUT/one_rank_rccl_gather_bench.json"
 if [ "${3:-fuzz}" = "fuzz" ]; then
   timeout 900 python scripts/gpu_fuzz_fast.py 400 32 > "$OUT/fuzz_fast_400_seed32.txt" 2>&1; tail -1 "$OUT/fuzz_fast_400_seed32.txt"
   timeout 1500 python scripts/gpu_fuzz_fast.py 800 77 > "$OUT/fuzz_fast_800_seed77.txt" 2>&1; tail -1 "$OUT/fuzz_fast_800_seed77.txt"

@@ -18,7 +18,7 @@ if [ "${2:-tests}" = "tests" ]; then
   cp gpurun_out/cfo_curve_*.json "$OUT/" 2>/dev/null
 fi
 cd /tmp && export TMPDIR=/tmp
-[ "$MODE" = "c8only" ] || python $R/bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+[ "$MODE" = "c8only" ] || python $R/bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 KRE='_kernel'   # counters only on the library's kernels (all named *_kernel): rocprofv3 crashed inside torch's randn / mul_ launches of the C8 capture generator
 pmc() { # name slots bench-args...   -> $OUT/<name>_pmc_hbm.json, _pmc_sq.txt, _pmc_stall.txt, _kernel_stats.csv, _timeline.txt
   n=$1; slots=$2; shift; shift
@@ -38,7 +38,7 @@ pmc() { # name slots bench-args...   -> $OUT/<name>_pmc_hbm.json, _pmc_sq.txt, _
 [ "$MODE" = "c8only" ] || pmc c79 2304
 if [ "$MODE" = "c8only" ]; then
 pmc c8 16384 --workload c8 --steps 100 --synth-device cpu
-python $R/bench.py --workload c8 --steps 100 --no-cpu --no-block-config --no-ab --no-host-fed --pmc-json "$OUT/c8_pmc_hbm.json" > "$OUT/c8_bench_with_traffic.json" 2> "$OUT/c8.err"
+python $R/bench.py --full --workload c8 --steps 100 --no-cpu --no-block-config --no-ab --no-host-fed --pmc-json "$OUT/c8_pmc_hbm.json" > "$OUT/c8_bench_with_traffic.json" 2> "$OUT/c8.err"
 cat "$OUT/c8_pmc_hbm.json" | head -c 1500; tail -1 "$OUT/c8_bench_with_traffic.json" | cut -c1-600; exit 0
 fi
 if [ "$MODE" = "full" ]; then
@@ -46,14 +46,14 @@ pmc block 2304 --le --headers --exact-payload
 pmc c8 16384 --workload c8 --steps 100 --synth-device cpu      # (the PMC passes crash inside torch's randn launches of the GPU generator)
 fi
 # the bench line again: picks the PMC summary up when it sits under profiles/ (here: passed explicitly)
-python $R/bench.py --no-cpu --no-block-config --no-ab --no-host-fed --pmc-json "$OUT/c79_pmc_hbm.json" > "$OUT/bench_with_traffic.json" 2>> "$OUT/bench.err"
+python $R/bench.py --full --no-cpu --no-block-config --no-ab --no-host-fed --pmc-json "$OUT/c79_pmc_hbm.json" > "$OUT/bench_with_traffic.json" 2>> "$OUT/bench.err"
 if [ "$MODE" = "full" ]; then
 C8J=""; python -c "import json,sys; json.load(open(sys.argv[1]))" "$OUT/c8_pmc_hbm.json" 2>/dev/null && C8J="--pmc-json $OUT/c8_pmc_hbm.json"
-python $R/bench.py --workload c8 --steps 100 $C8J > "$OUT/c8_bench.json" 2> "$OUT/c8.err"
+python $R/bench.py --full --workload c8 --steps 100 $C8J > "$OUT/c8_bench.json" 2> "$OUT/c8.err"
 # N > 1 path on this one device: two ranks, time-partitioned, gathered (gloo), and the single-rank RCCL group
 cd $R
-python bench.py --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
-python bench.py --gpus 1 --force-gather --backend nccl --no-cpu --no-block-config --no-ab --no-host-fed 2> "$OUT/one_rank_rccl.err" | head -1 > "$OUT/one_rank_rccl_gather_bench.json"
+python bench.py --full --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
+python bench.py --full --gpus 1 --force-gather --backend nccl --no-cpu --no-block-config --no-ab --no-host-fed 2> "$OUT/one_rank_rccl.err" | head -1 > "$OUT/one_rank_rccl_gather_bench.json"
 fi
 cd $R
 if [ "$MODE" = "full" ]; then

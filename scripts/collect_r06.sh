@@ -17,7 +17,7 @@ if [ "${2:-tests}" = "tests" ]; then
 fi
 if [ "$MODE" != "pmc" ]; then for u in exact_mfma mfma_rate mfma_overlap mfma_shadow; do [ -x scripts/ubench/$u ] && ./scripts/ubench/$u > "$OUT/ubench_$u.txt" 2>&1; done; fi
 cd /tmp && export TMPDIR=/tmp
-[ "$MODE" = "pmc" ] || python $R/bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+[ "$MODE" = "pmc" ] || python $R/bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 KRE='_kernel'   # counters only on the library's kernels (all named *_kernel)
 n=c79; slots=2304
 rm -rf /tmp/kt_$n /tmp/p1_$n /tmp/p2_$n /tmp/p3_$n /tmp/p4_$n /tmp/p5_$n
@@ -35,11 +35,11 @@ python $R/scripts/pmc_table.py "$(find /tmp/p4_$n -name '*counter_collection.csv
 rocprofv3 --kernel-include-regex "$KRE" --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE SQ_ACTIVE_INST_SCA --output-format csv -d /tmp/p5_$n -o p -- $PM > /dev/null 2>> "$OUT/bench.err"
 python $R/scripts/pmc_table.py "$(find /tmp/p5_$n -name '*counter_collection.csv' | head -1)" > "$OUT/${n}_pmc_mfma.txt" 2>> "$OUT/bench.err"
 # the bench line again with the traffic of this very build
-python $R/bench.py --no-cpu --no-block-config --no-c8 --no-exact-all --no-ab --no-host-fed --pmc-json "$OUT/c79_pmc_hbm.json" > "$OUT/bench_with_traffic.json" 2>> "$OUT/bench.err"
+python $R/bench.py --full --no-cpu --no-block-config --no-c8 --no-exact-all --no-ab --no-host-fed --pmc-json "$OUT/c79_pmc_hbm.json" > "$OUT/bench_with_traffic.json" 2>> "$OUT/bench.err"
 cd $R
 if [ "$MODE" = "full" ]; then
-  python bench.py --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu --no-c8 > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
-  python bench.py --gpus 1 --force-gather --backend nccl --no-cpu --no-block-config --no-c8 --no-ab --no-host-fed 2> "$OUT/one_rank_rccl.err" | head -1 > "$OUT/one_rank_rccl_gather_bench.json"
+  python bench.py --full --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu --no-c8 > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
+  python bench.py --full --gpus 1 --force-gather --backend nccl --no-cpu --no-block-config --no-c8 --no-ab --no-host-fed 2> "$OUT/one_rank_rccl.err" | head -1 > "$OUT/one_rank_rccl_gather_bench.json"
   timeout 1500 python scripts/gpu_fuzz_adversarial.py 1000 31001 > "$OUT/fuzz_adversarial_1000_seed31001.txt" 2>&1; tail -1 "$OUT/fuzz_adversarial_1000_seed31001.txt"
   timeout 900 python scripts/gpu_fuzz_adversarial.py 400 31002 --wide --rates 4,10,16,40,50,100 > "$OUT/fuzz_adversarial_wide_400_seed31002.txt" 2>&1; tail -1 "$OUT/fuzz_adversarial_wide_400_seed31002.txt"
   timeout 1200 python scripts/gpu_judge_seamless.py 1500 32001 > "$OUT/judge_seamless_mix_1500_seed32001.txt" 2>&1; tail -1 "$OUT/judge_seamless_mix_1500_seed32001.txt"

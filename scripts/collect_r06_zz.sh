@@ -15,10 +15,10 @@ cat "$OUT/second_handle.txt"
 # the exact rows' kernel alone, the rotating A operand (the library's form) against three 16-byte groups ahead (-DBTGPU_EX_FULLA=0), 4 / 9 / 20 channels per tile
 for u in exact_mfma exact_mfma_e0; do [ -x scripts/ubench/$u ] && for pt in 4 9 20; do echo "== $u, $pt channels per tile"; ./scripts/ubench/$u $pt 2304 0 2048 | grep "^mode"; done; done > "$OUT/ubench_exact_full_a_ab.txt" 2>&1
 cat "$OUT/ubench_exact_full_a_ab.txt"
-python bench.py --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu --no-c8 --no-exact-all > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
-python bench.py --gpus 1 --force-gather --backend nccl --no-cpu --no-block-config --no-c8 --no-ab --no-host-fed --no-exact-all 2> "$OUT/one_rank_rccl.err" | head -1 > "$OUT/one_rank_rccl_gather_bench.json"
+python bench.py --full --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu --no-c8 --no-exact-all > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
+python bench.py --full --gpus 1 --force-gather --backend nccl --no-cpu --no-block-config --no-c8 --no-ab --no-host-fed --no-exact-all 2> "$OUT/one_rank_rccl.err" | head -1 > "$OUT/one_rank_rccl_gather_bench.json"
 cd /tmp && export TMPDIR=/tmp
-BENCH_DUMP_STEPS=1 python $R/bench.py --workload c8 --no-cpu --no-block-config --no-exact-all --no-ab --no-host-fed --full-timing --steps 40 > "$OUT/c8_full_timing.json" 2> "$OUT/c8.err"
+BENCH_DUMP_STEPS=1 python $R/bench.py --full --workload c8 --no-cpu --no-block-config --no-exact-all --no-ab --no-host-fed --full-timing --steps 40 > "$OUT/c8_full_timing.json" 2> "$OUT/c8.err"
 rm -rf /tmp/kt_c8
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_c8 -o kt -- python $R/bench.py --workload c8 --no-cpu --no-block-config --no-exact-all --no-ab --no-host-fed --no-timing --steps 40 > "$OUT/c8_bench_under_rocprof.json" 2>> "$OUT/c8.err"
 python $R/scripts/summarize_rocprof.py "$(find /tmp/kt_c8 -name '*kernel_stats.csv' | head -1)" "$OUT/c8_kernel_stats.csv"

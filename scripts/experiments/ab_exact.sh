@@ -7,7 +7,7 @@ cp gr-bluetooth_amd/libbtgpu.so /tmp/libbtgpu_base.so
 for r in $(seq ${2:-2}); do
   for v in $1; do
     if [ "$v" = base ]; then cp /tmp/libbtgpu_base.so gr-bluetooth_amd/libbtgpu.so; else cp gr-bluetooth_amd/libbtgpu_$v.so gr-bluetooth_amd/libbtgpu.so; fi
-    python bench.py --no-cpu --no-block-config --no-c8 --no-exact-all --no-ab --no-host-fed 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().split('\n')[-1]); print(sys.argv[1], 'value', j['value'], 'ms', j['ms_per_step'], 'exact', j['roofline']['avg_launch_ms'], 'bank', j['roofline_bank']['avg_launch_ms'], 'records', j['parity']['records_sha256'], j['parity']['hits'])" $v
+    python bench.py --full --no-cpu --no-block-config --no-c8 --no-exact-all --no-ab --no-host-fed 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().split('\n')[-1]); print(sys.argv[1], 'value', j['value'], 'ms', j['ms_per_step'], 'exact', j['roofline']['avg_launch_ms'], 'bank', j['roofline_bank']['avg_launch_ms'], 'records', j['parity']['records_sha256'], j['parity']['hits'])" $v
   done
 done
 cp /tmp/libbtgpu_base.so gr-bluetooth_amd/libbtgpu.so

@@ -15,12 +15,12 @@ bash scripts/collect_profiles.sh $TAG > "$OUT/collect.log" 2>&1
 tail -1 "$OUT/bench.json" | cut -c1-300
 # C8 (BASELINE configs[1]): bench line + kernel stats
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py --workload c8 --steps 100 > "$OUT/c8_bench.json" 2> "$OUT/c8.err"
+python $R/bench.py --full --workload c8 --steps 100 > "$OUT/c8_bench.json" 2> "$OUT/c8.err"
 rm -rf /tmp/kt8
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt8 -o kt -- python $R/bench.py --workload c8 --steps 100 --no-cpu > "$OUT/c8_bench_under_rocprof.json" 2>> "$OUT/c8.err"
 python $R/scripts/summarize_rocprof.py "$(find /tmp/kt8 -name '*kernel_stats.csv' | head -1)" "$OUT/c8_kernel_stats.csv"
 cut -c1-200 "$OUT/c8_bench.json"
 # N > 1 path on this one device: two ranks, time-partitioned, gathered once per batch
 cd $R
-python bench.py --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
+python bench.py --full --gpus 2 --all-on-device0 --backend gloo --slots 1152 --no-cpu > "$OUT/two_rank_on_one_device_bench.json" 2> "$OUT/two_rank.err"
 cut -c1-200 "$OUT/two_rank_on_one_device_bench.json"

@@ -719,7 +719,7 @@ def test_bench_two_ranks_on_one_device_equal_one_rank(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu",
+    base = [sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu",
             "--prewarm-ms", "5", "--occupancy", "0.5", "--no-c8", "--no-block-config", "--no-ab", "--no-host-fed"]
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -944,7 +944,7 @@ def test_rccl_gather_path_single_rank(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--no-cpu",
+    base = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", "4", "--warmup", "1", "--no-cpu",
             "--prewarm-ms", "5", "--occupancy", "0.5", "--slots", "96", "--no-block-config", "--gather-every", "1"]
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -963,6 +963,35 @@ def test_rccl_gather_path_single_rank(tmp_path):
     assert j1["parity"]["hits"] == j0["parity"]["hits"]
     assert j1["parity"]["records_sha256"] == j0["parity"]["records_sha256"]
     assert j1["ms_per_step_by_rank"] and len(j1["ms_per_step_by_rank"]) == 1
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_records(tmp_path):
+    """`bench.py` without --full: the K timed steps of the headline region and nothing behind them -- the line carries value and
+    ms_per_step for exactly --steps steps and none of the --full legs -- and --dump-outputs writes the last timed step's record
+    set (one copy, float64, rows ascending) beside its snr_db."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm-ms", "5",
+                          "--occupancy", "0.5", "--slots", "48", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, env=env, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    j = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][-1])
+    assert (j["metric"], j["unit"], j["higher_is_better"], j["dtype"]) == ("complex-IQ Msamples/s @ 79 ch", "Msamples/s", True, "f32")
+    assert j["steps"] == 3 and j["ms_per_step"] > 0
+    # value and ms_per_step are one measurement (ms_per_step is printed to 0.001 ms: half a unit of that on a step of >= 0.05 ms)
+    assert j["ms_per_step"] >= 0.05 and abs(j["value"] - j["config"]["samples_per_rank_per_step"] / j["ms_per_step"] / 1e3) <= 1e-2 * j["value"]
+    for leg in ("roofline", "roofline_bank", "cpu_baseline", "parity", "classic_only", "c8", "exact_all", "verify", "host_fed"):
+        assert leg not in j, leg
+    rec, snr = np.load(tmp_path / "out" / "records.npy"), np.load(tmp_path / "out" / "snr_db.npy")
+    assert rec.dtype == np.float64 and snr.dtype == np.float64 and rec.ndim == 2 and rec.shape[1] == 7 and snr.shape == (len(rec),)
+    assert len(rec) > 40 and np.array_equal(rec, np.round(rec))
+    assert 0 <= rec[:, 0].min() and rec[:, 0].max() < 48 and 0 <= rec[:, 1].min() and rec[:, 1].max() < 79
+    rows = [tuple(r) for r in rec]
+    assert rows == sorted(rows) and len(set(rows)) == len(rows)              # one copy of the step's set, not the K steps' stream
 
 
 @pytest.mark.parametrize("fs,fc,nslots", [(8e6, 2476.5e6, 40), (20e6, 2441e6, 24), (4e6, 2476e6, 40), (50e6, 2441e6, 12)])
