@@ -17,6 +17,7 @@
 #include "design.h"
 #include "kernels.hip.h"
 #include "pfb100.hip.h"
+#include "s16_inst.h"        // the int16-input kernels: declared here, compiled in s16_kernels.hip
 #include "bank_launch.h"
 #include "hopseq.hip.h"
 
@@ -110,7 +111,7 @@ struct btgpu_handle {
     bool no_nsym = false;            // BTGPU_FLAG_NO_NSYM: skip the M&M continuation that produces hit.nsym
     int verify = 0;                  // exact rows under the polyphase path's records (exact.hip.h): 0 off, 1 presence + uncovered hits, 2 uncovered hits only
     int vcap = 0, bm_tiles = 0;
-    ExactRowsKernel ex_kern = nullptr; size_t ex_lds = 0;
+    ExactRowsKernel ex_kern = nullptr, ex_kern_s16 = nullptr; size_t ex_lds = 0;   // exact rows on a float / an int16 input stream
     bool exact_all = false;          // BTGPU_FLAG_EXACT_ALL: every row of every channel is recomputed (no presence)
     std::vector<const void *> lds_opted;   // bank kernels that have been granted > 48 KiB of dynamic LDS on this handle's device
     DevBuf d_tapsA;                  // the direct-form channel bank's taps as exact_rows_kernel's A operand (exact_pack_taps)
@@ -277,9 +278,11 @@ struct btgpu_handle {
     hipEvent_t ev_vdone[2] = {nullptr, nullptr};      // the batch's tail (whose exact stage re-reads the input) has left the tail stream
     bool stage_used[2] = {false, false};
     unsigned stage_turn = 0;
-    int stage_batch(const float *head, size_t n_head_zero, const float *body, size_t n_body, long long w0,
-                    uint64_t abs_first_slot, int S);
-    int process_batch(const float2 *d_x, size_t x_len, long long w0, uint64_t abs_first_slot, int S, hipStream_t st);
+    // s16: the input format of this call -- interleaved int16 (4 bytes per complex sample) instead of float32.  A property of
+    // the CALL, not of the handle: it picks the kernels' int16 instantiations and halves the bytes staged; `head` is float always.
+    int stage_batch(const float *head, size_t n_head_zero, const void *body, size_t n_body, long long w0,
+                    uint64_t abs_first_slot, int S, bool s16 = false);
+    int process_batch(const float2 *d_x, size_t x_len, long long w0, uint64_t abs_first_slot, int S, hipStream_t st, bool s16 = false);
     int harvest(TailCtx &t);
     int harvest_all(bool block);
 };
@@ -288,7 +291,7 @@ struct btgpu_handle {
 // one batch of S slots; d_x[w0] = first sample of window 0 of the batch, d_x[0..w0) = margin
 // ---------------------------------------------------------------------------------------
 int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, uint64_t abs_first_slot,
-                                int S, hipStream_t st)
+                                int S, hipStream_t st, bool s16)
 {
     const btgpu_design &d = des.d;
     const int nch = d.high_channel - d.low_channel + 1;
@@ -319,6 +322,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
     if (verify) HIPCHK(this, hipMemsetAsync(t.d_vcount.p, 0, kVerCountWords * sizeof(unsigned int), st));
     HIPCHK(this, mark(0, st));
     int ntiles = 0, tiles_per_block = 1, tail_tiles = 0;
+    const auto ddc = s16 ? ddc_direct_kernel_s16<2> : ddc_direct_kernel<2>;   // the direct-form bank for this call's input format
     bool fused_m = false;                                       // small-M banks: stage 1 ran inside the channel bank's kernel
 
     // ---- channel bank -> demodulated stream d[g][nch] + |Y|^2 tile sums (polyphase) or block sums P, Pt (direct) ----
@@ -331,7 +335,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
         // whole GPU suite has run with it: bit-identical outputs under the emulator and in the 8 Msps GPU tests, profiles/r04_v_*
         static const bool fuse_m_on = getenv("BTGPU_C8_FUSE") && atoi(getenv("BTGPU_C8_FUSE")) == 1;
         fused_m = fuse_m_on && use_staged && noise_small && pfbm_fuse_noise(des, fp, S, G, drow);
-        ntiles = launch_channel_bank_m(des, fp, bb, x_len, w0, G, L, fused_m ? S : 0);
+        ntiles = launch_channel_bank_m(des, fp, bb, x_len, w0, G, L, fused_m ? S : 0, s16);
         tiles_per_block = ops / pfbm_tile(fp.channel.M); tail_tiles = des.tail / pfbm_tile(fp.channel.M);
         HIPCHK(this, mark(1, st));
     } else if (use_pfb) {
@@ -360,14 +364,14 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
                    v == "run512" ? (int)kBankRun512 : v == "run512r" ? (int)kBankRun512r : v == "run256d" ? (int)kBankRun256d :
                    v == "run256e" ? (int)kBankRun256e : v == "run256a" ? (int)kBankRun256a : (int)kBankRun256;
         }();
-        ntiles = launch_channel_bank(des, fp, fuse_noise, bb, x_len, w0, S, G, nb, L, variant);
+        ntiles = launch_channel_bank(des, fp, fuse_noise, bb, x_len, w0, S, G, nb, L, variant, s16);
         tiles_per_block = ops / TT; tail_tiles = des.tail / TT;
         HIPCHK(this, mark(1, st));
     } else {
         const LaunchShape &s = shape_ch;
         const unsigned gx = seg_ch ? (unsigned)(((seg_ch + s.T - 1) / s.T) * S) : (unsigned)((G + s.T - 1) / s.T);
         dim3 grid(gx, (unsigned)((nch + 1) / 2));
-        hipLaunchKernelGGL(ddc_direct_kernel<2>, grid, dim3(s.T), s.lds, st, d_x, (long long)x_len,
+        hipLaunchKernelGGL(ddc, grid, dim3(s.T), s.lds, st, d_x, (long long)x_len,
                            w0 + (long long)d.first_channel_sample, d.decimation, des.channel.ntp, s.JC,
                            (const float2 *)d_taps_ch.p, (const float2 *)d_rot_ch.p, des.channel.rot_period,
                            (const double *)d_rotstep_ch.p, (float2 *)d_Y.p, G, ystride, nch, seg_ch, seg_stride);
@@ -392,18 +396,18 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
             auto L = [&](void (*kern)(PfbParams), int grid, int threads, size_t lds, const PfbParams &p) {
                 hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)threads), lds, st, p);
             };
-            launch_noise_bank(des, fp, bb, x_len, w0, S, L);
+            launch_noise_bank(des, fp, bb, x_len, w0, S, L, s16);
         } else if (noise_small) {
             BankBuffers bb = bank_buffers(d_x, t);
             auto L = [&](void (*kern)(PfbmParams), int grid, int threads, size_t lds, const PfbmParams &p) {
                 hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)threads), lds, st, p);
             };
-            launch_noise_bank_m(des, fp, bb, x_len, w0, S, L);
+            launch_noise_bank_m(des, fp, bb, x_len, w0, S, L, s16);
         } else {
             // stage 1 as a direct-form bank: B-spline prototype (a few hundred taps at most), hop R
             const LaunchShape &s = shape_s1;
             dim3 grid((unsigned)((Tn + s.T - 1) / s.T), (unsigned)((nch + 1) / 2));
-            hipLaunchKernelGGL(ddc_direct_kernel<2>, grid, dim3(s.T), s.lds, st, d_x, (long long)x_len, xs0, ns.R,
+            hipLaunchKernelGGL(ddc, grid, dim3(s.T), s.lds, st, d_x, (long long)x_len, xs0, ns.R,
                                ns.direct.ntp, s.JC, (const float2 *)d_taps_s1.p, (const float2 *)d_rot_s1.p,
                                ns.direct.rot_period, (const double *)d_rotstep_s1.p, (float2 *)t.d_Z.p, Tn, zstride, nch, 0, 0LL);
         }
@@ -413,7 +417,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
         const LaunchShape &s = shape_n;
         const unsigned gx = seg_n ? (unsigned)(((seg_n + s.T - 1) / s.T) * S) : (unsigned)((Gn + s.T - 1) / s.T);
         dim3 grid(gx, (unsigned)((nch + 1) / 2));
-        hipLaunchKernelGGL(ddc_direct_kernel<2>, grid, dim3(s.T), s.lds, st, d_x, (long long)x_len,
+        hipLaunchKernelGGL(ddc, grid, dim3(s.T), s.lds, st, d_x, (long long)x_len,
                            w0 + (long long)d.first_noise_sample, d.decimation, des.noise.ntp, s.JC,
                            (const float2 *)d_taps_n.p, (const float2 *)d_rot_n.p, des.noise.rot_period,
                            (const double *)d_rotstep_n.p, (float2 *)d_Yn.p, Gn, ystride_n, nch, seg_n, seg_stride);
@@ -459,7 +463,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
     auto launch_exact_rows = [&](const uint32_t *bitmap, unsigned int *stat, hipStream_t s_) {
         const ExactParams ep = make_exact_params(des, x_len, w0, G, (const float *)d_tapsA.p, (const float2 *)d_rot_ch.p, (const float *)d_atan.p,
                                                  bitmap, vb.bm_tiles, (float *)d_d.p, drow, (float *)(use_dcol ? t.d_dcol.p : nullptr), stat);
-        hipLaunchKernelGGL(ex_kern, dim3((unsigned)vb.bm_tiles), dim3(kExThreads), ex_lds, s_, ep, d_x);
+        hipLaunchKernelGGL(s16 ? ex_kern_s16 : ex_kern, dim3((unsigned)vb.bm_tiles), dim3(kExThreads), ex_lds, s_, ep, d_x);
     };
     if (verify && exact_all) {
         hipLaunchKernelGGL(exact_mark_all_kernel, dim3((unsigned)((vb.bm_tiles * kExBmWords + 255) / 256)), dim3(256), 0, ps, vb.bm1, vb.bm_tiles, nch);
@@ -627,9 +631,12 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
 // kernels.  `head` (may be null) supplies real samples for the first n_head samples instead of zeros when the
 // caller has them (the margin carried between btgpu_work calls).  Buffers alternate; a buffer is reused only
 // after the batch that read it has left the main stream.
-int btgpu_handle::stage_batch(const float *head, size_t n_head, const float *body, size_t n_body, long long w0,
-                              uint64_t abs_first_slot, int S)
+// int16 input (s16): the same two pinned and two device buffers, at 4 bytes per complex sample instead of 8; `head` stays float
+// (the margin carried between work calls is kept widened) and is narrowed back here -- exact for what an int16 call left there.
+int btgpu_handle::stage_batch(const float *head, size_t n_head, const void *body, size_t n_body, long long w0,
+                              uint64_t abs_first_slot, int S, bool s16)
 {
+    const size_t ssz = s16 ? 2 * sizeof(int16_t) : sizeof(float2);              // bytes per complex sample
     const unsigned k = stage_turn++ & 1u;
     const size_t cap = in_cap + (size_t)margin + 64;
     if (n_head + n_body > cap) { set_error("staging overflow"); return BTGPU_EINVAL; }
@@ -646,12 +653,15 @@ int btgpu_handle::stage_batch(const float *head, size_t n_head, const float *bod
         HIPCHK(this, hipEventSynchronize(ev_consumed[k]));
         if (verify) HIPCHK(this, hipEventSynchronize(ev_vdone[k]));
     }
-    float *dst = (float *)h_stage[k];
+    char *dst = (char *)h_stage[k];
     if (n_head) {
-        if (head) std::memcpy(dst, head, n_head * sizeof(float2));
-        else std::memset(dst, 0, n_head * sizeof(float2));
+        if (head && s16) {
+            int16_t *d16 = (int16_t *)dst;
+            for (size_t i = 0; i < 2 * n_head; i++) d16[i] = (int16_t)std::lrintf(std::min(32767.f, std::max(-32768.f, head[i])));
+        } else if (head) std::memcpy(dst, head, n_head * ssz);
+        else std::memset(dst, 0, n_head * ssz);                                  // (int16 zeros are zero bytes too)
     }
-    float2 *d_buf = (float2 *)(k == 0 ? d_in.p : d_in_b.p);
+    char *d_buf = (char *)(k == 0 ? d_in.p : d_in_b.p);
     // A caller's buffer that is page-locked already (hipHostMalloc / hipHostRegister: what a block can do once with the
     // scheduler's buffer) is copied to the device as it lies -- no pass through the staging buffer; the call
     // then returns when that copy is done (the buffer is the caller's again), the kernels of this and the previous batches
@@ -663,19 +673,19 @@ int btgpu_handle::stage_batch(const float *head, size_t n_head, const float *bod
         // page-locked from its first byte to its last (a buffer registered only in part would be copied as if all of it were: ADVICE r4)
         if (n_body > 0 && hipPointerGetAttributes(&attr, body) == hipSuccess && attr.type == hipMemoryTypeHost) {
             hipPointerAttribute_t last;
-            if (hipPointerGetAttributes(&last, (const char *)body + n_body * sizeof(float2) - 1) == hipSuccess && last.type == hipMemoryTypeHost) direct = true;
+            if (hipPointerGetAttributes(&last, (const char *)body + n_body * ssz - 1) == hipSuccess && last.type == hipMemoryTypeHost) direct = true;
             else (void)hipGetLastError();
         } else (void)hipGetLastError();                                      // (an unregistered pointer is reported as an error: cleared)
         static const bool no_direct = getenv("BTGPU_NO_DIRECT_H2D") != nullptr;
         if (no_direct) direct = false;
     }
     if (direct) {
-        if (n_head) HIPCHK(this, hipMemcpyAsync(d_buf, h_stage[k], n_head * sizeof(float2), hipMemcpyHostToDevice, copy_stream));
-        HIPCHK(this, hipMemcpyAsync(d_buf + n_head, body, n_body * sizeof(float2), hipMemcpyHostToDevice, copy_stream));
+        if (n_head) HIPCHK(this, hipMemcpyAsync(d_buf, h_stage[k], n_head * ssz, hipMemcpyHostToDevice, copy_stream));
+        HIPCHK(this, hipMemcpyAsync(d_buf + n_head * ssz, body, n_body * ssz, hipMemcpyHostToDevice, copy_stream));
     } else {
-        const size_t bytes = n_body * sizeof(float2);
+        const size_t bytes = n_body * ssz;
         const unsigned nthr = bytes >= ((size_t)64 << 20) ? std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
-        if (nthr <= 1) std::memcpy(dst + 2 * n_head, body, bytes);
+        if (nthr <= 1) std::memcpy(dst + n_head * ssz, body, bytes);
         else {
             std::vector<std::thread> pool;
             const size_t chunk = (bytes / nthr + 4095) & ~(size_t)4095;
@@ -683,15 +693,15 @@ int btgpu_handle::stage_batch(const float *head, size_t n_head, const float *bod
                 const size_t o = (size_t)i * chunk;
                 if (o >= bytes) break;
                 const size_t len = std::min(chunk, bytes - o);
-                pool.emplace_back([=] { std::memcpy((char *)(dst + 2 * n_head) + o, (const char *)body + o, len); });
+                pool.emplace_back([=] { std::memcpy(dst + n_head * ssz + o, (const char *)body + o, len); });
             }
             for (auto &th : pool) th.join();
         }
-        HIPCHK(this, hipMemcpyAsync(d_buf, h_stage[k], (n_head + n_body) * sizeof(float2), hipMemcpyHostToDevice, copy_stream));
+        HIPCHK(this, hipMemcpyAsync(d_buf, h_stage[k], (n_head + n_body) * ssz, hipMemcpyHostToDevice, copy_stream));
     }
     HIPCHK(this, hipEventRecord(ev_copied[k], copy_stream));
     HIPCHK(this, hipStreamWaitEvent(stream, ev_copied[k], 0));
-    const int rc = process_batch(d_buf, n_head + n_body, w0, abs_first_slot, S, stream);
+    const int rc = process_batch((const float2 *)d_buf, n_head + n_body, w0, abs_first_slot, S, stream, s16);
     // (behind the enqueue: the kernels queue up under the copy; also where process_batch failed -- the buffer is the caller's again
     // only once the copy has left it)
     if (direct) { const hipError_t se = hipEventSynchronize(ev_copied[k]); if (rc != BTGPU_OK) return rc; HIPCHK(this, se); }
@@ -1239,9 +1249,10 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         std::vector<float> ta(exact_taps_floats(nch, d.decimation));
         exact_pack_taps(des.channel.taps.data(), nch, des.channel.ntp, d.decimation, ta.data());
         TRY(h->upload(h->d_tapsA, ta.data(), ta.size() * sizeof(float)));
-        h->ex_kern = exact_rows_pick(d.decimation); h->ex_lds = exact_lds_bytes(d.decimation);
+        h->ex_kern = exact_rows_pick(d.decimation); h->ex_kern_s16 = exact_rows_pick<true>(d.decimation); h->ex_lds = exact_lds_bytes(d.decimation);
         h->bm_tiles = exact_ntiles(h->ystride + 64);
         (void)hipFuncSetAttribute((const void *)h->ex_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(h->ex_lds, 64 * 1024));
+        (void)hipFuncSetAttribute((const void *)h->ex_kern_s16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(h->ex_lds, 64 * 1024));
     }
     for (int i = 0; i < h->nctx; i++) {
         auto &t = h->tc[i];
@@ -1323,6 +1334,23 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
     (void)hipFuncSetAttribute((const void *)pfb100f_kernel<kBankThreads, true, 2 * kBankKT, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     (void)hipFuncSetAttribute((const void *)pfb100f_kernel<kBankThreads, true, 2 * kBankKT, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     (void)hipFuncSetAttribute((const void *)pfb100f_kernel<kBankThreads, false, 2 * kBankKT, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    // ... and for their int16-input twins (the run kernel's are opted in next to their launch, like the float ones)
+    (void)hipFuncSetAttribute((const void *)ddc_direct_kernel_s16<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<7, 1, 26, true, true, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<7, 1, 26, false, true, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<7, 1, 26, true, true, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<7, 1, 26, false, true, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<15, 5, 10, false, false, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, true, 8, 7, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, true, 8, 7, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<true, true, 8, 7, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, true, 8, 7, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<true, true, 20, 7, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<true, true, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, true, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, false, 8, 15, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, false, 8, 15, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, false, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     h->pre.assign((size_t)h->margin * 2, 0.f);
     if (getenv("BTGPU_VERBOSE"))
         fprintf(stderr, "btgpu_create: %d contexts, d=%p Z=%p ptile=%p\n", h->nctx, h->tc[0].d_d.p, h->tc[0].d_Z.p, h->tc[0].d_ptile.p);
@@ -1358,10 +1386,13 @@ int btgpu_device_count(void)
 }
 const char *btgpu_last_error(const btgpu_handle *h) { return h ? h->err.c_str() : "null handle"; }
 
-int btgpu_process_device(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
-                         uint64_t first_slot, uint64_t n_slots, void *hip_stream)
+// The three input entries in both formats: s16 = interleaved int16 behind the pointer (4 bytes per complex sample), n in complex
+// samples either way.
+static int process_device_any(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
+                              uint64_t first_slot, uint64_t n_slots, void *hip_stream, bool s16)
 {
     if (!h || !d_iq) return BTGPU_EINVAL;
+    if (s16 && ((uintptr_t)d_iq & 7u)) return BTGPU_EINVAL;      // the banks load int16 samples in aligned pairs (btgpu.h)
     const btgpu_design &d = h->des.d;
     if (n_slots == 0) return BTGPU_OK;
     const size_t need = left_margin + (size_t)d.history + (size_t)(n_slots - 1) * d.samples_per_slot;
@@ -1372,17 +1403,28 @@ int btgpu_process_device(btgpu_handle *h, const void *d_iq, size_t n_complex, si
     for (uint64_t s0 = 0; s0 < n_slots; s0 += (uint64_t)h->max_slots) {
         const int S = (int)std::min<uint64_t>((uint64_t)h->max_slots, n_slots - s0);
         const long long w0 = (long long)left_margin + (long long)s0 * d.samples_per_slot;
-        int rc = h->process_batch((const float2 *)d_iq, n_complex, w0, first_slot + s0, S, st);
+        int rc = h->process_batch((const float2 *)d_iq, n_complex, w0, first_slot + s0, S, st, s16);
         if (rc == BTGPU_EOVERFLOW) rc_all = rc;
         else if (rc != BTGPU_OK) return rc;
     }
     return rc_all;
 }
+int btgpu_process_device(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
+                         uint64_t first_slot, uint64_t n_slots, void *hip_stream)
+{
+    return process_device_any(h, d_iq, n_complex, left_margin, first_slot, n_slots, hip_stream, false);
+}
+int btgpu_process_device_s16(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
+                             uint64_t first_slot, uint64_t n_slots, void *hip_stream)
+{
+    return process_device_any(h, d_iq, n_complex, left_margin, first_slot, n_slots, hip_stream, true);
+}
 
-int btgpu_process_host(btgpu_handle *h, const float *iq, size_t n_complex, size_t left_margin, uint64_t first_slot,
-                       uint64_t n_slots)
+static int process_host_any(btgpu_handle *h, const void *iq, size_t n_complex, size_t left_margin, uint64_t first_slot,
+                            uint64_t n_slots, bool s16)
 {
     if (!h || !iq) return BTGPU_EINVAL;
+    const size_t ssz = s16 ? 2 * sizeof(int16_t) : 2 * sizeof(float);
     const btgpu_design &d = h->des.d;
     if (n_slots == 0) return BTGPU_OK;
     const size_t H = (size_t)d.history, slot = (size_t)d.samples_per_slot, mg = (size_t)h->margin;
@@ -1394,16 +1436,28 @@ int btgpu_process_host(btgpu_handle *h, const float *iq, size_t n_complex, size_
         const size_t seg = H + (size_t)(S - 1) * slot;
         const size_t i0 = left_margin + (size_t)s0 * slot;           // sample index of window 0 of this batch
         const size_t have = std::min(mg, i0), zeros = mg - have;     // real samples in front, else implied zeros
-        int rc = h->stage_batch(nullptr, zeros, iq + 2 * (i0 - have), have + seg, (long long)mg, first_slot + s0, S);
+        int rc = h->stage_batch(nullptr, zeros, (const char *)iq + (i0 - have) * ssz, have + seg, (long long)mg, first_slot + s0, S, s16);
         if (rc == BTGPU_EOVERFLOW) rc_all = rc;
         else if (rc != BTGPU_OK) return rc;
     }
     return rc_all;
 }
-
-int btgpu_work(btgpu_handle *h, const float *items, size_t n_items, size_t *consumed)
+int btgpu_process_host(btgpu_handle *h, const float *iq, size_t n_complex, size_t left_margin, uint64_t first_slot,
+                       uint64_t n_slots)
 {
-    if (!h || !items) return BTGPU_EINVAL;
+    return process_host_any(h, iq, n_complex, left_margin, first_slot, n_slots, false);
+}
+int btgpu_process_host_s16(btgpu_handle *h, const int16_t *iq, size_t n_complex, size_t left_margin, uint64_t first_slot,
+                           uint64_t n_slots)
+{
+    return process_host_any(h, iq, n_complex, left_margin, first_slot, n_slots, true);
+}
+
+static int work_any(btgpu_handle *h, const void *items_, size_t n_items, size_t *consumed, bool s16)
+{
+    if (!h || !items_) return BTGPU_EINVAL;
+    const size_t ssz = s16 ? 2 * sizeof(int16_t) : 2 * sizeof(float);
+    const float *items = (const float *)items_; const int16_t *items16 = (const int16_t *)items_;
     const btgpu_design &d = h->des.d;
     if (consumed) *consumed = 0;
     const size_t H = (size_t)d.history, slot = (size_t)d.samples_per_slot, mg = (size_t)h->margin;
@@ -1419,7 +1473,7 @@ int btgpu_work(btgpu_handle *h, const float *items, size_t n_items, size_t *cons
         size_t from_items = std::min(mg, i0), from_pre = mg - from_items;
         // pre holds the mg samples before items[0]; its last from_pre samples come first
         int rc = h->stage_batch(from_pre ? h->pre.data() + 2 * (mg - from_pre) : nullptr, from_pre,
-                                items + 2 * (i0 - from_items), from_items + seg, (long long)mg, h->push_slot + s0, S);
+                                (const char *)items_ + (i0 - from_items) * ssz, from_items + seg, (long long)mg, h->push_slot + s0, S, s16);
         if (rc == BTGPU_EOVERFLOW) rc_all = rc;
         else if (rc != BTGPU_OK) return rc;
     }
@@ -1429,6 +1483,7 @@ int btgpu_work(btgpu_handle *h, const float *items, size_t n_items, size_t *cons
         std::vector<float> np(2 * mg);
         for (size_t i = 0; i < mg; i++) {
             long long src = (long long)used - (long long)mg + (long long)i;      // item index, may be < 0 -> old pre
+            if (src >= 0 && s16) { np[2 * i] = (float)items16[2 * src]; np[2 * i + 1] = (float)items16[2 * src + 1]; continue; }   // (kept widened: exact)
             const float *pp = src >= 0 ? items + 2 * src : h->pre.data() + 2 * (mg + src);
             np[2 * i] = pp[0]; np[2 * i + 1] = pp[1];
         }
@@ -1437,6 +1492,8 @@ int btgpu_work(btgpu_handle *h, const float *items, size_t n_items, size_t *cons
     if (consumed) *consumed = used;
     return rc_all;
 }
+int btgpu_work(btgpu_handle *h, const float *items, size_t n_items, size_t *consumed) { return work_any(h, items, n_items, consumed, false); }
+int btgpu_work_s16(btgpu_handle *h, const int16_t *items, size_t n_items, size_t *consumed) { return work_any(h, items, n_items, consumed, true); }
 
 int btgpu_push(btgpu_handle *h, const float *iq, size_t n_complex)
 {

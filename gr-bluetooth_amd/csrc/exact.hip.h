@@ -103,8 +103,18 @@ inline size_t exact_taps_floats(int nch, int D) { return (size_t)nch * 64 * exac
 // per tile, 3.89 -> 3.72 at twenty, 1.21 -> 1.20 at four; in the bench's step 2.14 -> 2.04 ms, records identical
 // (profiles/r06_zz_ubench_exact_full_a_ab.txt, r06_zz_exact_full_a_ab_bench.txt).
 constexpr bool exact_full_a(int D) { return BTGPU_EX_FULLA && D > 25; }
-template <int D>
-__global__ __launch_bounds__(kExThreads, exact_full_a(D) ? 3 : 4) void exact_rows_kernel(ExactParams p, const float2 *__restrict__ x)
+// S16: the input stream is interleaved int16 (kernels.hip.h).  The B operand of a lane is then the 2-byte re or im half of D
+// consecutive 4-byte samples.  Chosen: D SIGNED 2-BYTE LOADS (global_load_sshort) at a 4-byte stride, each followed by one
+// integer -> float conversion -- the float form's D loads with the stride halved.  Against 4-, 8- or 16-byte loads of whole
+// samples with a bit-field extract per element: (1) the load unit sign-extends for nothing, while every extract is one more
+// vector instruction per element, and this kernel's time is its matrix time PLUS every other instruction's issue time (F12
+// above); (2) a 2-byte load asks no alignment of first0 and of the stream's base beyond the sample's own 2 bytes, where the
+// 8- and 16-byte forms would need a scalar prologue per lane (column starts s0 = sb + D m have either parity for odd D);
+// (3) the wide form was tried on the float stream (16-byte loads, the lane keeps its half) and measured the same
+// (profiles/r06_u_*): what bounds this load is the number of lanes' addresses the texture unit walks, and both half-waves
+// of a 2-byte load fall into the same 64-byte lines.  The clamped edge branch widens whole samples one by one.
+template <int D, bool S16>
+__device__ __forceinline__ void exact_rows_body(const ExactParams &p, const float2 *__restrict__ x)
 {
     HIP_DYNAMIC_SHARED(float2, lds)
     constexpr int NS = 32 * D;                                     // samples per wave
@@ -146,14 +156,20 @@ __global__ __launch_bounds__(kExThreads, exact_full_a(D) ? 3 : 4) void exact_row
             if (sb >= 0 && sb + NS <= p.x_len) {                   // uniform: the wave's span lies inside the stream
                 // (16-byte loads -- two samples, the lane keeps its half -- cost the texture unit a quarter of this form's work per tile and
                 // measured the same: 2.09 ms against 2.07, profiles/r06_u_*)
+                if constexpr (S16) {
+                    const int16_t *xh = (const int16_t *)x + 2 * s0 + (lane >> 5);
+#pragma unroll
+                    for (int r = 0; r < D; r++) B[r] = (float)xh[2 * r];
+                } else {
                 const float *xf = (const float *)(x + s0) + (lane >> 5);
 #pragma unroll
                 for (int r = 0; r < D; r++) B[r] = xf[2 * r];
+                }
             } else {
 #pragma unroll
                 for (int r = 0; r < D; r++) {
                     const long long a = s0 + r;
-                    const float2 t = x[a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1)];
+                    const float2 t = load_sample<S16>(x, a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1));
                     B[r] = (a >= 0 && a < p.x_len) ? ((lane >> 5) ? t.y : t.x) : 0.f;
                 }
             }
@@ -270,16 +286,27 @@ __global__ __launch_bounds__(kExThreads, exact_full_a(D) ? 3 : 4) void exact_row
         }
     }
 }
+template <int D>
+__global__ __launch_bounds__(kExThreads, exact_full_a(D) ? 3 : 4) void exact_rows_kernel(ExactParams p, const float2 *__restrict__ x)
+{
+    exact_rows_body<D, false>(p, x);
+}
+template <int D>
+__global__ __launch_bounds__(kExThreads, exact_full_a(D) ? 3 : 4) void exact_rows_kernel_s16(ExactParams p, const float2 *__restrict__ x)
+{
+    exact_rows_body<D, true>(p, x);
+}
 
 typedef void (*ExactRowsKernel)(ExactParams, const float2 *);
 // the instantiations: D = fs / 2 MHz for the rates the polyphase banks serve (4 .. 50 Msps: D = 2 .. 25; 100 Msps: D = 50)
 // (Round 6 also built a vector-lane form for D <= 4 -- a lane = an output row, its 14 D samples in registers, the taps as scalar
 // operands, no LDS and no barrier per channel -- bit-identical to this kernel on 164 M rows and SLOWER: 2.58 ms against 2.05 for
 // 145 M rows at D = 4 (profiles/r06_t_ubench_exact.txt); removed.)
+template <bool S16 = false>
 inline ExactRowsKernel exact_rows_pick(int D)
 {
     switch (D) {
-#define BTGPU_EX(n) case n: return exact_rows_kernel<n>;
+#define BTGPU_EX(n) case n: if constexpr (S16) return exact_rows_kernel_s16<n>; else return exact_rows_kernel<n>;
         BTGPU_EX(2) BTGPU_EX(3) BTGPU_EX(4) BTGPU_EX(5) BTGPU_EX(6) BTGPU_EX(7) BTGPU_EX(8) BTGPU_EX(9) BTGPU_EX(10) BTGPU_EX(11) BTGPU_EX(12) BTGPU_EX(13)
         BTGPU_EX(14) BTGPU_EX(15) BTGPU_EX(16) BTGPU_EX(17) BTGPU_EX(18) BTGPU_EX(19) BTGPU_EX(20) BTGPU_EX(21) BTGPU_EX(22) BTGPU_EX(23) BTGPU_EX(24) BTGPU_EX(25)
         BTGPU_EX(50)

@@ -67,6 +67,45 @@ constexpr int kVerRows = 1416;    // rows of a window the exact stage's clock re
 constexpr int kVerTile = 127;     // new demodulated rows per tile of verify_ddc_kernel (128 outputs, the first is the demod halo)
 
 // ------------------------------------------------------------------------------------
+// Input formats of the stream x.  Every kernel that reads x has its body templated on S16 (false: x is interleaved float32,
+// 8 bytes per complex sample).  S16 = true: x points at interleaved int16 (re in the low half of a
+// 32-bit word, im in the high half, 4 bytes per sample) and is widened HERE, at the load, with (float)int16 and no scale
+// factor -- int16 -> float32 is exact, so everything behind the load sees the bits the float form would have seen.  The
+// pointer keeps its type (const float2 *) in every parameter block and signature; it is reinterpreted in these helpers only.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ float2 s16_widen(uint32_t w)          // one sample: sign-extend both halves, convert
+{
+    return make_float2((float)(int16_t)(w & 0xffffu), (float)((int32_t)w >> 16));
+}
+template <bool S16>
+__device__ __forceinline__ float2 load_sample(const float2 *x, long long i)
+{
+    if constexpr (S16) return s16_widen(((const uint32_t *)x)[i]);
+    else return x[i];
+}
+// samples i, i + 1 as one load: 16 bytes (float) or 8 bytes (int16); i even and x aligned to that size
+template <bool S16>
+__device__ __forceinline__ float4 load_sample_pair(const float2 *x, long long i)
+{
+    if constexpr (S16) {
+        const uint2 w = *(const uint2 *)((const uint32_t *)x + i);
+        const float2 a = s16_widen(w.x), b = s16_widen(w.y);
+        return make_float4(a.x, a.y, b.x, b.y);
+    } else return *(const float4 *)(x + i);
+}
+
+// the same pair held RAW in registers (what the bank kernels prefetch a tile ahead: half the registers with int16) and widened
+// just before the LDS write
+template <bool S16> struct InPiece { typedef float4 type; };
+template <> struct InPiece<true> { typedef uint2 type; };
+__device__ __forceinline__ float4 piece_widen(const float4 &q) { return q; }
+__device__ __forceinline__ float4 piece_widen(const uint2 &w)
+{
+    const float2 a = s16_widen(w.x), b = s16_widen(w.y);
+    return make_float4(a.x, a.y, b.x, b.y);
+}
+
+// ------------------------------------------------------------------------------------
 // K1: direct-form decimating complex band-pass FIR bank (channel bank and noise bank).
 //   y[c][g] = ( sum_j taps[c][j] * x[first + g*D + j] ) * rot[c][g]
 // Summation order (bit-exact contract with the oracle's ddc_run and with exact.hip.h, which runs the same order on the matrix
@@ -77,8 +116,10 @@ constexpr int kVerTile = 127;     // new demodulated rows per tile of verify_ddc
 // workgroup's tile is staged through LDS once per tap chunk and shared by the CPB
 // channels; taps are wave-uniform (scalar loads).
 // ------------------------------------------------------------------------------------
-template <int CPB>
-__global__ __launch_bounds__(256) void ddc_direct_kernel(
+// (The kernels proper are thin: X_kernel<...> is the float-input form under its old name, X_kernel_s16<...> the int16-input form of
+// the same body -- a trailing template parameter would have renamed every existing kernel.)
+template <int CPB, bool S16>
+__device__ __forceinline__ void ddc_direct_body(
     const float2 *__restrict__ x, long long x_len, long long first, int D, int ntp, int JC,
     const float2 *__restrict__ taps, const float2 *__restrict__ rot, int Q,
     const double *__restrict__ rot_step_turns,   // used when Q == 0
@@ -123,7 +164,7 @@ __global__ __launch_bounds__(256) void ddc_direct_kernel(
             for (int k = 0; k < 4; k++) {
                 const long long a = base + s0 + k * T;
                 const long long ac = a < 0 ? 0 : (a < x_len ? a : x_len - 1);
-                v[k] = x[ac];
+                v[k] = load_sample<S16>(x, ac);
             }
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -180,6 +221,16 @@ __global__ __launch_bounds__(256) void ddc_direct_kernel(
         Y[(size_t)c * ystride + gout] = out;
     }
 }
+#define BTGPU_DDC_PARAMS const float2 *__restrict__ x, long long x_len, long long first, int D, int ntp, int JC, const float2 *__restrict__ taps, \
+    const float2 *__restrict__ rot, int Q, const double *__restrict__ rot_step_turns, float2 *__restrict__ Y, long long G, long long ystride, int nch, \
+    int seg_len, long long seg_stride
+#define BTGPU_DDC_ARGS x, x_len, first, D, ntp, JC, taps, rot, Q, rot_step_turns, Y, G, ystride, nch, seg_len, seg_stride
+template <int CPB>
+__global__ __launch_bounds__(256) void ddc_direct_kernel(BTGPU_DDC_PARAMS) { ddc_direct_body<CPB, false>(BTGPU_DDC_ARGS); }
+template <int CPB>
+__global__ __launch_bounds__(256) void ddc_direct_kernel_s16(BTGPU_DDC_PARAMS) { ddc_direct_body<CPB, true>(BTGPU_DDC_ARGS); }
+#undef BTGPU_DDC_PARAMS
+#undef BTGPU_DDC_ARGS
 
 // ------------------------------------------------------------------------------------
 // gr::fast_atan2f [EXT GNU Radio 3.7], table in LDS/global (257 floats)

@@ -146,8 +146,11 @@ __device__ __forceinline__ void setprio_dyn(int v)
 // OPT 512 (NTH = 512 only): four waves per SIMD, i.e. two workgroups per CU in <= 128 registers, instead of six in 80
 // OPT (experiments, A/B on the device): 1 = epilogue not fenced, 2 = march reads 8 steps ahead, 4 = packed channel MACs,
 // 8 = lean epilogue (needs rho = +-1: p.rho_real), 16 = epilogue instants in lockstep pairs on whole tiles, 32 = the DFT passes at raised wave priority, 64 = staging / stores too (2), 128 = epilogue at 1
-template <int NTH, bool REAL, int KT, int OPT = 0>
-__global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 320 ? 4 : 3)) void pfb100f_kernel(PfbParams p)   // (HIP: the second number is waves per SIMD)
+// S16: the input stream is interleaved int16 (kernels.hip.h): a lane's prefetched piece is 8 bytes instead of 16 for the same two
+// samples, kept raw in (half as many) registers across the tile and widened at the LDS write; the edge tiles widen sample by
+// sample.  LDS layout and everything behind the staging are the float form's.
+template <int NTH, bool REAL, int KT, int OPT, bool S16>
+__device__ __forceinline__ void pfb100f_body(const PfbParams &p)
 {
     static_assert(NTH == 256 || NTH == 320 || NTH == 512, "lane roles are laid out for four, five or eight waves");
     constexpr bool SPLIT = NTH == 512;                           // eight waves: channel branches on waves 0..3, squelch branches on waves 4..7
@@ -243,15 +246,19 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 3
     // are staged in place when their turn comes, element by element with clamped addresses (zeros outside).
     // (named registers, not an array: an array that lives across the tile loop stays in scratch memory)
     static_assert(PER <= 6, "explicit prefetch registers below");
-    float4 v0, v1, v2, v3, v4, v5;
-    v0 = v1 = v2 = v3 = v4 = v5 = make_float4(0.f, 0.f, 0.f, 0.f);
+    typedef typename InPiece<S16>::type PV;                      // two samples as they lie in the stream: 16 bytes, or 8 (int16)
+    constexpr unsigned PB = (unsigned)sizeof(PV);
+    PV v0, v1, v2, v3, v4, v5;
+    if constexpr (S16) v0 = v1 = v2 = v3 = v4 = v5 = PV{};
+    else v0 = v1 = v2 = v3 = v4 = v5 = make_float4(0.f, 0.f, 0.f, 0.f);
     auto load_span = [&](int tile, int l) {
         // uniform base + 32-bit lane offset (scalar base registers, no 64-bit lane arithmetic); only the last piece clamps
-        const char *xb = (const char *)(p.x + span_start(tile));
-        const unsigned o = (unsigned)l * 16u;
+        // (span_start is even: every piece is a naturally aligned load as long as the stream's base is aligned to a piece)
+        const char *xb = S16 ? (const char *)((const uint32_t *)p.x + span_start(tile)) : (const char *)(p.x + span_start(tile));
+        const unsigned o = (unsigned)l * PB;
         auto at = [&](int j) {
-            const unsigned oj = (j + 1) * NTH <= N4 ? o : (unsigned)(l + j * NTH < N4 ? l : N4 - 1 - j * NTH) * 16u;
-            return *(const float4 *)(xb + (size_t)j * NTH * 16 + oj);
+            const unsigned oj = (j + 1) * NTH <= N4 ? o : (unsigned)(l + j * NTH < N4 ? l : N4 - 1 - j * NTH) * PB;
+            return *(const PV *)(xb + (size_t)j * NTH * PB + oj);
         };
         v0 = at(0); if (PER > 1) v1 = at(1); if (PER > 2) v2 = at(2); if (PER > 3) v3 = at(3);
         if (PER > 4) v4 = at(4); if (PER > 5) v5 = at(5);
@@ -262,7 +269,7 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 3
         for (int i = l; i < N4; i += NTH) {
             const long long s0 = a0 + 2LL * i, s1 = s0 + 1;
             const bool in0 = s0 >= 0 && s0 < p.x_len, in1 = s1 >= 0 && s1 < p.x_len;
-            const float2 q0 = p.x[in0 ? s0 : 0], q1 = p.x[in1 ? s1 : 0];
+            const float2 q0 = load_sample<S16>(p.x, in0 ? s0 : 0), q1 = load_sample<S16>(p.x, in1 ? s1 : 0);
             ((float4 *)xs)[i] = make_float4(in0 ? q0.x : 0.f, in0 ? q0.y : 0.f, in1 ? q1.x : 0.f, in1 ? q1.y : 0.f);
         }
     };
@@ -363,7 +370,7 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 3
         if (OPT & 256) setprio_dyn((p.dbg >> 8) & 15);
         else if (OPT & 64) __builtin_amdgcn_s_setprio(2);        // (staging + the previous tile's stores: little arithmetic)
         if (interior(tile)) {
-            auto put = [&](int j, const float4 &q) { const int i = l + j * NTH; if (i < N4) ((float4 *)xs)[i] = q; };
+            auto put = [&](int j, const PV &q) { const int i = l + j * NTH; if (i < N4) ((float4 *)xs)[i] = piece_widen(q); };
             put(0, v0); if (PER > 1) put(1, v1); if (PER > 2) put(2, v2); if (PER > 3) put(3, v3);
             if (PER > 4) put(4, v4); if (PER > 5) put(5, v5);
         } else stage_edge(tile, l);
@@ -620,6 +627,16 @@ __global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 3
         mark(4);                                         // angle tiles complete; Y (= the span region) is dead
     }
     if (prev_any) flush_prev(prev_tile, prev_u0, l0);
+}
+template <int NTH, bool REAL, int KT, int OPT = 0>
+__global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 320 ? 4 : 3)) void pfb100f_kernel(PfbParams p)   // (HIP: the second number is waves per SIMD)
+{
+    pfb100f_body<NTH, REAL, KT, OPT, false>(p);
+}
+template <int NTH, bool REAL, int KT, int OPT = 0>
+__global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 320 ? 4 : 3)) void pfb100f_kernel_s16(PfbParams p)
+{
+    pfb100f_body<NTH, REAL, KT, OPT, true>(p);
 }
 
 }  // namespace btgpu

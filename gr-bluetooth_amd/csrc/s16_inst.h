@@ -1,0 +1,55 @@
+// s16_inst.h -- the int16-input instantiations of the kernels that read the input stream (kernels.hip.h "Input formats").
+//
+// They are compiled in a translation unit of their own (s16_kernels.hip): btgpu.hip sees them as explicit instantiation
+// DECLARATIONS (extern template) and only takes their addresses through bank_launch.h's helpers, exact_rows_pick<true> and
+// its own ddc_direct_kernel launches.  One list, two uses: BTGPU_S16_INSTANTIATE defined -> definitions, else declarations.
+// A launch helper that picks an int16 kernel missing from this list fails at link time, not at run time.
+#pragma once
+#include "kernels.hip.h"
+#include "pfb100.hip.h"
+#include "pfb100f.hip.h"
+#include "pfbm.hip.h"
+#include "exact.hip.h"
+
+namespace btgpu {
+
+#ifdef BTGPU_S16_INSTANTIATE
+#define BTGPU_S16_KERNEL(...) template __global__ void __VA_ARGS__;   // (the only symbols the library exports: s16_kernels.map)
+#else
+#define BTGPU_S16_KERNEL(...) extern template __global__ void __VA_ARGS__;
+#endif
+
+// direct-form bank: DIRECT channelizer and squelch, segmented rates, the staged squelch's direct stage 1
+BTGPU_S16_KERNEL(ddc_direct_kernel_s16<2>(const float2 *, long long, long long, int, int, int, const float2 *, const float2 *, int,
+                                            const double *, float2 *, long long, long long, int, int, long long))
+// 100-bin bank, runs of tiles (launch_channel_bank's default forms)
+BTGPU_S16_KERNEL(pfb100f_kernel_s16<256, true, 10, 255>(PfbParams))
+BTGPU_S16_KERNEL(pfb100f_kernel_s16<256, true, 10, 231>(PfbParams))
+BTGPU_S16_KERNEL(pfb100f_kernel_s16<256, false, 10, 227>(PfbParams))
+// 100-bin bank, one tile per workgroup: fused (the run kernel's fallback), channel bank alone, stand-alone squelch stage 1
+BTGPU_S16_KERNEL(pfb100_kernel_s16<7, 1, 26, true, true, 256, true>(PfbParams))
+BTGPU_S16_KERNEL(pfb100_kernel_s16<7, 1, 26, false, true, 256, true>(PfbParams))
+BTGPU_S16_KERNEL(pfb100_kernel_s16<7, 1, 26, true, true, 256, false>(PfbParams))
+BTGPU_S16_KERNEL(pfb100_kernel_s16<7, 1, 26, false, true, 256, false>(PfbParams))
+BTGPU_S16_KERNEL(pfb100_kernel_s16<15, 5, 10, false, false, 256, false>(PfbParams))
+// small-M banks (launch_channel_bank_m, launch_noise_bank_m)
+BTGPU_S16_KERNEL(pfbm_kernel_s16<false, true, 8, 7, true, true>(PfbmParams))
+BTGPU_S16_KERNEL(pfbm_kernel_s16<false, true, 8, 7, true, false>(PfbmParams))
+BTGPU_S16_KERNEL(pfbm_kernel_s16<true, true, 8, 7, true, false>(PfbmParams))
+BTGPU_S16_KERNEL(pfbm_kernel_s16<false, true, 8, 7, false, false>(PfbmParams))
+BTGPU_S16_KERNEL(pfbm_kernel_s16<true, true, 20, 7, false, false>(PfbmParams))
+BTGPU_S16_KERNEL(pfbm_kernel_s16<true, true, 0, 0, false, false>(PfbmParams))
+BTGPU_S16_KERNEL(pfbm_kernel_s16<false, true, 0, 0, false, false>(PfbmParams))
+BTGPU_S16_KERNEL(pfbm_kernel_s16<false, false, 8, 15, true, false>(PfbmParams))
+BTGPU_S16_KERNEL(pfbm_kernel_s16<false, false, 8, 15, false, false>(PfbmParams))
+BTGPU_S16_KERNEL(pfbm_kernel_s16<false, false, 0, 0, false, false>(PfbmParams))
+// exact rows: every decimation exact_rows_pick serves
+#define BTGPU_S16_EX(n) BTGPU_S16_KERNEL(exact_rows_kernel_s16<n>(ExactParams, const float2 *))
+BTGPU_S16_EX(2) BTGPU_S16_EX(3) BTGPU_S16_EX(4) BTGPU_S16_EX(5) BTGPU_S16_EX(6) BTGPU_S16_EX(7) BTGPU_S16_EX(8) BTGPU_S16_EX(9)
+BTGPU_S16_EX(10) BTGPU_S16_EX(11) BTGPU_S16_EX(12) BTGPU_S16_EX(13) BTGPU_S16_EX(14) BTGPU_S16_EX(15) BTGPU_S16_EX(16) BTGPU_S16_EX(17)
+BTGPU_S16_EX(18) BTGPU_S16_EX(19) BTGPU_S16_EX(20) BTGPU_S16_EX(21) BTGPU_S16_EX(22) BTGPU_S16_EX(23) BTGPU_S16_EX(24) BTGPU_S16_EX(25)
+BTGPU_S16_EX(50)
+#undef BTGPU_S16_EX
+#undef BTGPU_S16_KERNEL
+
+}  // namespace btgpu

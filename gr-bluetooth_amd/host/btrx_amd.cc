@@ -1,6 +1,7 @@
 // btrx_amd -- command-line driver, counterpart of the reference's apps/btrx for the two hot-path
 // blocks.  Same flag meanings (apps/btrx:22-60): -f centre frequency (default 2.476e9), -r sample
-// rate (required, >= 2e6), -i input file ('-' = stdin), -s input is interleaved int16, -N sample
+// rate (required, >= 2e6), -i input file ('-' = stdin), -s input is interleaved int16 (handed to the block as it is:
+// multi_block::set_input_shorts, widened on the GPU without scaling like interleaved_short_to_complex), -N sample
 // limit, -S all-piconet sniffer (default: LAP sniffer), -t SNR squelch (default 10.0),
 // -w Wireshark TAP sink.  The little scheduler below stands in for GNU Radio's: history()-1 zeros first,
 // work() called with a multiple of output_multiple() new items.  --gpus N (no counterpart in apps/btrx)
@@ -81,27 +82,30 @@ int main(int argc, char **argv)
         return 2;
     }
     const size_t H = blk->history(), mult = (size_t)blk->output_multiple();
-    std::vector<gr_complex> buf(H - 1, gr_complex(0, 0));          // GNU Radio pre-fills history()-1 zeros
-    std::vector<int16_t> sbuf;
+    std::vector<gr_complex> buf(shorts ? 0 : H - 1, gr_complex(0, 0));   // GNU Radio pre-fills history()-1 zeros
+    std::vector<int16_t> sbuf(shorts ? 2 * (H - 1) : 0, 0);        // -s: the items stay int16 (I, Q interleaved), the same zeros in front
+    if (shorts) blk->set_input_shorts();
+    // items held / appended, in either format
+    auto held = [&]() { return shorts ? sbuf.size() / 2 : buf.size(); };
+    auto read_items = [&](size_t want) {
+        const size_t old = held();
+        size_t got;
+        if (shorts) { sbuf.resize(2 * (old + want)); got = fread(&sbuf[2 * old], 2 * sizeof(int16_t), want, fp); sbuf.resize(2 * (old + got)); }
+        else { buf.resize(old + want); got = fread(&buf[old], sizeof(gr_complex), want, fp); buf.resize(old + got); }
+        return got;
+    };
     if (gpus > 1) {
         // whole capture in memory, one time range per device
         for (;;) {
             size_t want = (size_t)1 << 22;
-            if (nsamples >= 0 && (double)(buf.size() - (H - 1)) + (double)want > nsamples) want = (size_t)(nsamples - (double)(buf.size() - (H - 1)));
+            if (nsamples >= 0 && (double)(held() - (H - 1)) + (double)want > nsamples) want = (size_t)(nsamples - (double)(held() - (H - 1)));
             if (want == 0) break;
-            size_t old = buf.size(), got;
-            buf.resize(old + want);
-            if (shorts) {
-                sbuf.resize(2 * want);
-                got = fread(sbuf.data(), 2 * sizeof(int16_t), want, fp);
-                for (size_t i = 0; i < got; i++) buf[old + i] = gr_complex(sbuf[2 * i], sbuf[2 * i + 1]);
-            } else got = fread(&buf[old], sizeof(gr_complex), want, fp);
-            buf.resize(old + got);
-            if (got < want) break;
+            if (read_items(want) < want) break;
         }
         if (fp != stdin) fclose(fp);
         try {
-            blk->run_partitioned(buf.data(), buf.size() - (H - 1), gpus, all_on_device0);
+            if (shorts) blk->run_partitioned(sbuf.data(), held() - (H - 1), gpus, all_on_device0);
+            else blk->run_partitioned(buf.data(), held() - (H - 1), gpus, all_on_device0);
         } catch (const std::exception &e) {
             fprintf(stderr, "%s\n", e.what());
             return 2;
@@ -115,25 +119,17 @@ int main(int argc, char **argv)
         size_t want = chunk;
         if (remaining >= 0 && (double)want > remaining) want = (size_t)remaining;
         if (want == 0) break;
-        size_t old = buf.size(), got;
-        buf.resize(old + want);
-        if (shorts) {
-            sbuf.resize(2 * want);
-            got = fread(sbuf.data(), 2 * sizeof(int16_t), want, fp);
-            for (size_t i = 0; i < got; i++) buf[old + i] = gr_complex(sbuf[2 * i], sbuf[2 * i + 1]);
-        } else {
-            got = fread(&buf[old], sizeof(gr_complex), want, fp);
-        }
-        buf.resize(old + got);
+        const size_t got = read_items(want);
         if (got < want) eof = true;
         if (remaining >= 0) remaining -= (double)got;
-        size_t avail = buf.size() - (H - 1);
+        size_t avail = held() - (H - 1);
         size_t n = avail / mult * mult;
         if (n == 0) continue;
-        gr_vector_const_void_star in(1, (const void *)buf.data());
+        gr_vector_const_void_star in(1, shorts ? (const void *)sbuf.data() : (const void *)buf.data());
         gr_vector_void_star out;
         int consumed = blk->work((int)n, in, out);
-        buf.erase(buf.begin(), buf.begin() + consumed);
+        if (shorts) sbuf.erase(sbuf.begin(), sbuf.begin() + 2 * (size_t)consumed);
+        else buf.erase(buf.begin(), buf.begin() + consumed);
     }
     if (fp != stdin) fclose(fp);
     return 0;

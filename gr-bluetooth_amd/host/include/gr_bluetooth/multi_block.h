@@ -41,6 +41,8 @@ protected:
     void drain(btgpu_handle *g);          // records of `g` -> handle_hit, in order
     btgpu_config d_cfg{};                 // what d_gpu was created with (run_partitioned clones it per device)
     int d_device = 0;                     // HIP ordinal d_gpu lives on
+    bool d_input_shorts = false;          // work()'s items are complex int16 (set_input_shorts)
+    long run_partitioned_any(const void *items, bool shorts, size_t n_new, int ngpus, bool all_on_device0);
 
 public:
     // Time-partitioned run over `ngpus` devices of this node (no GNU Radio counterpart: a flowgraph hands a
@@ -51,6 +53,13 @@ public:
     // i.e. in stream order -- and pass through the same per-record handlers on the calling thread.
     // all_on_device0: every range on device 0 (dry run on a one-GPU box).  Returns the items consumed.
     long run_partitioned(const gr_complex *items, size_t n_new, int ngpus, bool all_on_device0 = false);
+    // ... the same for a capture of complex int16 items (interleaved I, Q), which go to the devices as they are
+    long run_partitioned(const int16_t *items, size_t n_new, int ngpus, bool all_on_device0 = false);
+    // Declare, before the first work(), that input_items[0] holds complex int16 items (interleaved I, Q: what the
+    // reference's flowgraph feeds interleaved_short_to_complex) instead of gr_complex: work() then hands them to
+    // btgpu_work_s16 unconverted and unscaled -- half the bytes to the device, the same records.  (In a GNU Radio
+    // flowgraph the block's input signature is then a vector of two shorts per item.)
+    void set_input_shorts(bool on = true) { d_input_shorts = on; }
     double samples_per_slot() const { return d_design.samples_per_slot; }
     int low_channel() const { return d_design.low_channel; }
     int high_channel() const { return d_design.high_channel; }

@@ -202,7 +202,8 @@ const char *btgpu_last_error(const btgpu_handle *h);
 int btgpu_work(btgpu_handle *h, const float *items, size_t n_items, size_t *consumed);
 
 /* Streaming convenience: keeps history internally (zero pre-filled like the GNU Radio
- * scheduler) so arbitrary chunks can be pushed. */
+ * scheduler) so arbitrary chunks can be pushed.  Float input only: the history it carries is float32 (there is no
+ * btgpu_push_s16; an int16 source widens its chunks or calls btgpu_work_s16 on its own buffer). */
 int btgpu_push(btgpu_handle *h, const float *iq, size_t n_complex);
 
 /* Device-resident segment: d_iq[left_margin] is absolute sample
@@ -222,6 +223,23 @@ int btgpu_process_device(btgpu_handle *h, const void *d_iq, size_t n_complex, si
  * previous one (with BTGPU_FLAG_ASYNC).  Same layout and meaning of the arguments as btgpu_process_device. */
 int btgpu_process_host(btgpu_handle *h, const float *iq, size_t n_complex, size_t left_margin,
                        uint64_t first_slot, uint64_t n_slots);
+
+/* ---- complex int16 input (what the SDRs put on the wire; the reference's `btrx -s` / interleaved_short_to_complex) ----
+ * The three entries above for interleaved int16 I/Q, argument for argument: sizes, margins and slots stay in COMPLEX samples
+ * (one sample = two int16 = 4 bytes).  The samples travel to the device as they are -- half the bytes of the float entries --
+ * and are widened inside the kernels at their input loads with (float)int16, NO scale factor and no DC correction: int16 ->
+ * float32 is exact, so every record, the demodulated stream and the window energies are bit for bit what the float entry
+ * returns for the same values.  Every configuration btgpu_create accepts takes either format, and a handle may be fed
+ * either format from call to call (the margin btgpu_work carries between calls is kept as float32; an int16 call that
+ * follows a float call rounds those few samples to int16, saturating).
+ * Alignment: the kernels load int16 samples in aligned pairs, so the device pointer given to btgpu_process_device_s16 must
+ * be 8-byte aligned (BTGPU_EINVAL otherwise); host pointers need only the int16's own 2 bytes (they are staged into buffers
+ * of the library's own). */
+int btgpu_work_s16(btgpu_handle *h, const int16_t *items, size_t n_items, size_t *consumed);
+int btgpu_process_host_s16(btgpu_handle *h, const int16_t *iq, size_t n_complex, size_t left_margin,
+                           uint64_t first_slot, uint64_t n_slots);
+int btgpu_process_device_s16(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
+                             uint64_t first_slot, uint64_t n_slots, void *hip_stream);
 
 /* Drain queued hits, ordered by (slot, channel, kind, offset). Returns count (>=0) or <0. */
 int btgpu_poll(btgpu_handle *h, btgpu_hit *out, int max_hits);
