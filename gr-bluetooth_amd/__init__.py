@@ -34,6 +34,8 @@ FLAG_LE, FLAG_DEBUG_Y, FLAG_ASYNC, FLAG_SYMBOLS, FLAG_HEADERS, FLAG_TIMING, FLAG
 FLAG_NO_VERIFY = 256      # polyphase path without the exact confirmation of its records (A/B)
 FLAG_EXACT_PAYLOAD = 512  # exported symbols exact to the end of the packet (include/btgpu.h)
 FLAG_EXACT_ALL = 1024     # no selection: every row of every channel exact (include/btgpu.h)
+FLAG_EXACT_DENSE = 2048   # exact rows in the dense form also where the sparse one exists (include/btgpu.h)
+EXACT_NONE, EXACT_SPARSE, EXACT_DENSE = 0, 1, 2     # exact_form()
 KIND_AC, KIND_AA = 0, 1
 
 
@@ -85,7 +87,7 @@ EXPORTS = ["btgpu_design_query", "btgpu_acgen", "btgpu_filter_taps", "btgpu_stre
            "btgpu_hopseq_init_candidates", "btgpu_hopseq_winnow", "btgpu_hopseq_candidates", "btgpu_hopseq_lookup",
            "btgpu_hopseq_fetch", "btgpu_pending", "btgpu_flush", "btgpu_device", "btgpu_device_count", "btgpu_last_timing", "btgpu_debug_fetch",
            "btgpu_debug_scan_symbols", "btgpu_debug_lut", "btgpu_process_host",
-           "btgpu_work_s16", "btgpu_process_host_s16", "btgpu_process_device_s16"]
+           "btgpu_work_s16", "btgpu_process_host_s16", "btgpu_process_device_s16", "btgpu_exact_form"]
 
 
 class BtgpuError(RuntimeError):
@@ -193,6 +195,8 @@ def lib():
     L.btgpu_flush.argtypes = [vp]
     L.btgpu_last_timing.restype = ctypes.c_int
     L.btgpu_last_timing.argtypes = [vp, ctypes.POINTER(Timing)]
+    L.btgpu_exact_form.restype = ctypes.c_int
+    L.btgpu_exact_form.argtypes = [vp]
     L.btgpu_debug_fetch.restype = ctypes.c_long
     L.btgpu_debug_fetch.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, vp]
     L.btgpu_debug_tables.restype = ctypes.c_int
@@ -459,6 +463,10 @@ class _MultiBlock:
         t = Timing()
         self._L.btgpu_last_timing(self._h, ctypes.byref(t))
         return t
+
+    def exact_form(self):
+        """EXACT_NONE, EXACT_SPARSE or EXACT_DENSE: the form of the exact rows' kernel this block runs."""
+        return self._L.btgpu_exact_form(self._h)
 
     def debug_fetch(self, what, channel=0, first=0, count=0):
         dt = {0: np.complex64, 1: np.float32, 2: np.float64, 3: np.float64, 4: np.float64, 5: np.complex64,

@@ -287,9 +287,10 @@ inline void set_verify_flagging(WindowParams &p, const Design &des, const FastPa
     p.span_extra = headers ? 58 : 0;                     // 54 header symbols + the 4-symbol trailer
 }
 static_assert(kExactSlotRows == kExSlotRows, "design.h and kernels.hip.h agree on the slot");
-// exact_rows_kernel's parameters for one bitmap of the batch (tapsA: exact_pack_taps of the direct-form channel bank)
+// exact_rows_kernel's / exact_dense_kernel's parameters for one bitmap of the batch (tapsA: exact_pack_taps of the direct-form channel bank)
 inline ExactParams make_exact_params(const Design &des, size_t x_len, long long w0, long long G, const float *tapsA, const float2 *rot,
-                                     const float *atan_tab, const uint32_t *bitmap, int bm_tiles, float *d, int drow, float *dcol, unsigned int *stat)
+                                     const float *atan_tab, const uint32_t *bitmap, int bm_tiles, float *d, int drow, float *dcol, unsigned int *stat,
+                                     const float *tapsD = nullptr /* exact_pack_taps_dense: handles that run the dense form */)
 {
     const btgpu_design &dd = des.d;
     ExactParams e{};
@@ -297,6 +298,7 @@ inline ExactParams make_exact_params(const Design &des, size_t x_len, long long 
     e.tapsA = tapsA; e.rot = rot; e.Qr = des.channel.rot_period; e.atan_tab = atan_tab; e.gain = des.demod_gain;
     e.bitmap = bitmap; e.ntiles = bm_tiles; e.stat = stat; e.d = d; e.drow = drow; e.dcol = dcol;
     e.ydbg = nullptr; e.ystride = 0; e.nch = dd.high_channel - dd.low_channel + 1;
+    e.D = dd.decimation; e.tapsD = tapsD;
     return e;
 }
 inline VerifyFillParams make_verify_fill_params(const Design &des, const float *d_stream, const float *dcol, int drow, long long G,

@@ -115,6 +115,8 @@ struct btgpu_handle {
     bool exact_all = false;          // BTGPU_FLAG_EXACT_ALL: every row of every channel is recomputed (no presence)
     std::vector<const void *> lds_opted;   // bank kernels that have been granted > 48 KiB of dynamic LDS on this handle's device
     DevBuf d_tapsA;                  // the direct-form channel bank's taps as exact_rows_kernel's A operand (exact_pack_taps)
+    bool ex_dense = false;           // exact rows run in the dense form (exact_dense.hip.h): ex_kern / ex_kern_s16 are its kernels
+    DevBuf d_tapsD;                  // ... and its A operand (exact_pack_taps_dense); allocated on those handles only
     bool pipelined = false;          // front writes per-context buffers only: front(n+1) may overlap post(n)
     hipStream_t copy_stream = nullptr;
     hipStream_t spill_stream = nullptr;          // harvest: records beyond the eager copies (never behind an input copy)
@@ -218,7 +220,7 @@ struct btgpu_handle {
                          &d_Y, &d_Yn, &d_P, &d_Pt, &d_Q, &d_mmse, &d_atan, &d_aclo, &d_achi,
                          &d_le_hdr, &d_le_whiten, &d_le_index, &d_winbits,
                          &d_pfb_taps_ch, &d_pfb_tw, &d_binpos_ch, &d_binnat_ch, &d_rho_ch, &d_krot_ch, &d_b2map_fused, &d_b2map_fused_wide, &d_b2map_ch, &d_b2map_noise, &d_b2map_f320, &d_dftw_ch, &d_dftw_n,
-                         &d_pfb_taps_n, &d_binpos_n, &d_krot_n, &d_h3, &d_w, &d_taps_s1, &d_rot_s1, &d_rotstep_s1, &d_prof, &d_pcol, &d_wh18, &d_tapsA};
+                         &d_pfb_taps_n, &d_binpos_n, &d_krot_n, &d_h3, &d_w, &d_taps_s1, &d_rot_s1, &d_rotstep_s1, &d_prof, &d_pcol, &d_wh18, &d_tapsA, &d_tapsD};
         for (DevBuf *b : all) if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
         for (TailCtx &t : tc) {
             DevBuf *tb[] = {&t.d_winlen, &t.d_hits, &t.d_hitcount, &t.d_fin, &t.d_winfin, &t.d_symbits, &t.d_hdr, &t.d_d, &t.d_dcol,
@@ -462,7 +464,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
     }
     auto launch_exact_rows = [&](const uint32_t *bitmap, unsigned int *stat, hipStream_t s_) {
         const ExactParams ep = make_exact_params(des, x_len, w0, G, (const float *)d_tapsA.p, (const float2 *)d_rot_ch.p, (const float *)d_atan.p,
-                                                 bitmap, vb.bm_tiles, (float *)d_d.p, drow, (float *)(use_dcol ? t.d_dcol.p : nullptr), stat);
+                                                 bitmap, vb.bm_tiles, (float *)d_d.p, drow, (float *)(use_dcol ? t.d_dcol.p : nullptr), stat, (const float *)d_tapsD.p);
         hipLaunchKernelGGL(s16 ? ex_kern_s16 : ex_kern, dim3((unsigned)vb.bm_tiles), dim3(kExThreads), ex_lds, s_, ep, d_x);
     };
     if (verify && exact_all) {
@@ -1125,7 +1127,8 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
     if (h->use_pfb && getenv("BTGPU_VERIFY")) h->verify = std::max(0, std::min(2, atoi(getenv("BTGPU_VERIFY"))));
     // (exact rows on the shared grid need every window's rotator to start at exactly +-1 there -- true wherever the polyphase banks
     // exist: their channels sit on bins of fs / M, multiples of 0.5 MHz, i.e. of the 800 Hz a slot's rotation is periodic in)
-    if (h->verify && !(exact_rows_available(h->des) && exact_rows_pick(h->des.d.decimation))) {
+    // (the decimation is no condition: where exact_rows_pick has no instantiation -- D = 26 .. 49 -- the dense form runs)
+    if (h->verify && !exact_rows_available(h->des)) {
         if (cfg->channelizer == BTGPU_CHANNELIZER_POLYPHASE && !(cfg->flags & BTGPU_FLAG_NO_VERIFY)) return fail(BTGPU_EUNSUPPORTED);
         h->verify = 0;
     }
@@ -1246,10 +1249,25 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
     TRY(h->alloc(h->d_winbits, (size_t)((S + 2) / 3) * kBitWords * kWinThreads * sizeof(uint32_t)));   // most workgroups: 3 slots each
     if (h->verify) {
         h->vcap = verify_capacity(S, nch);
-        std::vector<float> ta(exact_taps_floats(nch, d.decimation));
-        exact_pack_taps(des.channel.taps.data(), nch, des.channel.ntp, d.decimation, ta.data());
-        TRY(h->upload(h->d_tapsA, ta.data(), ta.size() * sizeof(float)));
         h->ex_kern = exact_rows_pick(d.decimation); h->ex_kern_s16 = exact_rows_pick<true>(d.decimation); h->ex_lds = exact_lds_bytes(d.decimation);
+        // Which form (exact_dense.hip.h): dense where no sparse kernel is instantiated, on BTGPU_FLAG_EXACT_DENSE and on
+        // BTGPU_EXACT_FORM=dense; BTGPU_EXACT_FORM=sparse asks for the sparse form wherever it exists (A/B timing).  Otherwise
+        // sparse -- under BTGPU_FLAG_EXACT_ALL too: profiles/exact_dense_ab.json
+        {
+            const char *ef = getenv("BTGPU_EXACT_FORM");
+            h->ex_dense = !h->ex_kern || (cfg->flags & BTGPU_FLAG_EXACT_DENSE) != 0 || (ef && std::strcmp(ef, "dense") == 0);
+            if (ef && std::strcmp(ef, "sparse") == 0 && h->ex_kern) h->ex_dense = false;
+        }
+        if (h->ex_dense) {
+            std::vector<float> td(exact_dense_taps_floats(nch, d.decimation));
+            exact_pack_taps_dense(des.channel.taps.data(), nch, des.channel.ntp, d.decimation, td.data());
+            TRY(h->upload(h->d_tapsD, td.data(), td.size() * sizeof(float)));
+            h->ex_kern = exact_dense_kernel; h->ex_kern_s16 = exact_dense_kernel_s16<0>; h->ex_lds = exact_dense_lds_bytes(d.decimation);
+        } else {
+            std::vector<float> ta(exact_taps_floats(nch, d.decimation));
+            exact_pack_taps(des.channel.taps.data(), nch, des.channel.ntp, d.decimation, ta.data());
+            TRY(h->upload(h->d_tapsA, ta.data(), ta.size() * sizeof(float)));
+        }
         h->bm_tiles = exact_ntiles(h->ystride + 64);
         (void)hipFuncSetAttribute((const void *)h->ex_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(h->ex_lds, 64 * 1024));
         (void)hipFuncSetAttribute((const void *)h->ex_kern_s16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(h->ex_lds, 64 * 1024));
@@ -1577,6 +1595,12 @@ int btgpu_poll_headers(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr, uint8
     return poll_symbols_impl(h, out, hdr, symbols, sym_cap, sym_len, max_hits);
 }
 
+int btgpu_exact_form(const btgpu_handle *h)
+{
+    if (!h) return BTGPU_EINVAL;
+    return !h->verify ? BTGPU_EXACT_NONE : (h->ex_dense ? BTGPU_EXACT_DENSE : BTGPU_EXACT_SPARSE);
+}
+
 int btgpu_last_timing(const btgpu_handle *h, btgpu_timing *out)
 {
     if (!h || !out) return BTGPU_EINVAL;
@@ -1603,8 +1627,11 @@ long btgpu_debug_fetch(btgpu_handle *h, int what, int channel, size_t first, siz
             if (first >= avail) return 0;
             count = std::min(count, avail - first);
             if (hipSetDevice(h->device) != hipSuccess) return BTGPU_EDEVICE;
-            if (hipMemcpy2D(out, sizeof(float), (const float *)h->tc[h->last_ctx].d_d.p + first * h->drow + c, (size_t)h->drow * sizeof(float),
-                            sizeof(float), count, hipMemcpyDeviceToHost) != hipSuccess) return BTGPU_EDEVICE;
+            // (the rows as they lie, the channel's column picked on the host: a 2-D copy of 4-byte rows took ~70 ms per call)
+            std::vector<float> rows(count * (size_t)h->drow);
+            if (hipMemcpy(rows.data(), (const float *)h->tc[h->last_ctx].d_d.p + first * h->drow, rows.size() * sizeof(float),
+                          hipMemcpyDeviceToHost) != hipSuccess) return BTGPU_EDEVICE;
+            for (size_t i = 0; i < count; i++) ((float *)out)[i] = rows[i * h->drow + c];
             return (long)count;
         }
         case 7: src = h->tc[h->last_ctx].d_winlen.p; elem = sizeof(int); avail = (size_t)h->last_S * nch; break;

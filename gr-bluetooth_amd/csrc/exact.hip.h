@@ -57,6 +57,8 @@ struct ExactParams {
     float2 *ydbg; long long ystride;   // diagnostics: nullptr, or the de-rotated y [nch][ystride]
     int nch;
     int dbg;                      // timing experiments (scripts/ubench/exact_mfma.hip): 1 no stores, 2 no demodulator
+    int D;                        // the decimation, for the dense form (exact_dense.hip.h), whose kernels take it at run time
+    const float *tapsD;           // the dense form's A operand (exact_pack_taps_dense); nullptr on handles that run the sparse form
 };
 
 constexpr int exact_dpad(int D) { return (D + 3) / 4 * 4; }      // steps of a channel's A operand, padded to whole 16-byte groups
@@ -82,6 +84,34 @@ inline void exact_pack_taps(const float *taps, int nch, int ntp, int D, float *o
             }
 }
 inline size_t exact_taps_floats(int nch, int D) { return (size_t)nch * 64 * exact_dpad(D); }
+
+// The dense form's A operand (exact_dense.hip.h: CHANNELS are the matrix rows, one accumulation per tap block q):
+// out[((((b * kExQB + q) * (dpad / 4) + i) * 64 + l) * 4 + e] = the A operand of row block b, tap block q, step r = 4 i + e for lane l --
+// row l & 31 = 2 (c - 16 b) + (re: 0, im: 1) of channel c, k = l >> 5.  Same values, signs and swaps as exact_pack_taps: (tr, -ti)
+// for a re row, (ti, tr) for an im row, of tap j = q D + r; zero beyond the filter, beyond nch and in the pad.  A wave reads the
+// whole buffer front to back, a few groups ahead of use: kExDenseAhead zero groups at its end keep the last reads inside it.
+constexpr int kExDenseRows = 16;                                 // channels per 32-row block
+constexpr int kExDenseAhead = 4;
+constexpr int exact_dense_blocks(int nch) { return (nch + kExDenseRows - 1) / kExDenseRows; }
+inline size_t exact_dense_taps_floats(int nch, int D)
+{
+    return ((size_t)exact_dense_blocks(nch) * kExQB * (exact_dpad(D) / 4) + kExDenseAhead) * 256;
+}
+inline void exact_pack_taps_dense(const float *taps, int nch, int ntp, int D, float *out /* [blocks][kExQB][dpad / 4][64][4] + the zero groups */)
+{
+    const int DP = exact_dpad(D), nb = exact_dense_blocks(nch);
+    for (int b = 0; b < nb; b++)
+        for (int q = 0; q < kExQB; q++)
+            for (int r = 0; r < DP; r++)
+                for (int l = 0; l < 64; l++) {
+                    const int row = l & 31, kh = l >> 5, c = kExDenseRows * b + (row >> 1), im = row & 1, j = q * D + r;
+                    float tr = 0.f, ti = 0.f;
+                    if (r < D && c < nch && j < ntp) { tr = taps[((size_t)c * ntp + j) * 2]; ti = taps[((size_t)c * ntp + j) * 2 + 1]; }
+                    out[((((size_t)b * kExQB + q) * (DP / 4) + r / 4) * 64 + l) * 4 + (r & 3)] = im ? (kh ? tr : ti) : (kh ? -ti : tr);
+                }
+    float *z = out + (size_t)nb * kExQB * (DP / 4) * 256;
+    for (int i = 0; i < kExDenseAhead * 256; i++) z[i] = 0.f;
+}
 
 // Choreography of one tile: every wave fetches its 32 columns straight into D registers per lane (the B operand for every channel
 // of the tile; strided 4-byte loads, once per tile), then per channel ONE barrier:

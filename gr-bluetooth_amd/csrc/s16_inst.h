@@ -10,6 +10,7 @@
 #include "pfb100f.hip.h"
 #include "pfbm.hip.h"
 #include "exact.hip.h"
+#include "exact_dense.hip.h"
 
 namespace btgpu {
 
@@ -50,6 +51,8 @@ BTGPU_S16_EX(10) BTGPU_S16_EX(11) BTGPU_S16_EX(12) BTGPU_S16_EX(13) BTGPU_S16_EX
 BTGPU_S16_EX(18) BTGPU_S16_EX(19) BTGPU_S16_EX(20) BTGPU_S16_EX(21) BTGPU_S16_EX(22) BTGPU_S16_EX(23) BTGPU_S16_EX(24) BTGPU_S16_EX(25)
 BTGPU_S16_EX(50)
 #undef BTGPU_S16_EX
+// exact rows, dense form: one kernel for every decimation
+BTGPU_S16_KERNEL(exact_dense_kernel_s16<0>(ExactParams, const float2 *))
 #undef BTGPU_S16_KERNEL
 
 }  // namespace btgpu

@@ -83,7 +83,8 @@ extern "C" {
                                            default they are (exact rows, DESIGN.md sections 4.4 and 5): the records then equal the CPU
                                            reference's in slot, channel, kind, offset, LAP and ac_errors, and the symbols handed to the
                                            host layer are the reference's to the end of each packet; with this flag ~1e-4 .. 2e-2 of the
-                                           records (by traffic) come out a symbol apart or on one side only (the round-3 behaviour) */
+                                           records (by traffic) come out a symbol apart or on one side only (the round-3 behaviour).
+                                           Exact rows are served at every rate the polyphase channelizer is: 4 .. 64 and 100 Msps */
 
 #define BTGPU_FLAG_EXACT_PAYLOAD 0x200   /* accepted; ALWAYS ON since round 6.  The symbols a record hands to the host layer are the reference's
                                            own arithmetic to the END OF THE PACKET: a packet's air time is busy, so its rows are exact rows
@@ -94,7 +95,13 @@ extern "C" {
                                            direct-form arithmetic on the matrix pipe (presence marks everything): every field of every record,
                                            nsym and the records born from noise included, equals the CPU reference's with the bit-exact
                                            channelizer's (the squelch figure stays the staged filter's: SNR within 3.4e-6 dB).  ~8 Gsamples/s
-                                           at 79 channels / 100 Msps instead of ~30 */
+                                           at 79 channels / 100 Msps instead of ~30.  Honoured at every rate the
+                                           polyphase channelizer serves: 4 .. 64 Msps (52 .. 64 in the dense form only) and 100 Msps */
+
+#define BTGPU_FLAG_EXACT_DENSE 0x800     /* exact rows in their DENSE form (csrc/exact_dense.hip.h: 16 channels per matrix row block, the decimation a
+                                           run-time argument) also where the tile-sparse form exists.  The same bits in every row either way; the
+                                           dense form is what runs at 52 .. 64 Msps, where the sparse one is not instantiated.  The environment's
+                                           BTGPU_EXACT_FORM=dense | sparse does the same for A/B timing (profiles/exact_dense_ab.json) */
 
 #define BTGPU_KIND_AC 0
 #define BTGPU_KIND_AA 1
@@ -266,6 +273,12 @@ int btgpu_pending(const btgpu_handle *h);
 int btgpu_flush(btgpu_handle *h);
 
 int btgpu_last_timing(const btgpu_handle *h, btgpu_timing *out);
+
+/* Which form of the exact rows' kernel the handle runs (BTGPU_FLAG_EXACT_DENSE). */
+#define BTGPU_EXACT_NONE   0   /* no exact rows: DIRECT channelizer, or BTGPU_FLAG_NO_VERIFY */
+#define BTGPU_EXACT_SPARSE 1   /* exact_rows_kernel<D>: one (channel, tile) pair at a time    */
+#define BTGPU_EXACT_DENSE  2   /* exact_dense_kernel: channels as the matrix rows             */
+int btgpu_exact_form(const btgpu_handle *h);
 
 /* ---- introspection for parity tests: copies an intermediate of the LAST batch ----
  * what: 0 channel-bank output Y (complex64 [channel][g]; DIRECT channelizer or BTGPU_FLAG_DEBUG_Y),
