@@ -170,11 +170,12 @@ struct btgpu_handle {
     DevBuf d_in, d_in_b, d_taps_ch, d_taps_n, d_rot_ch, d_rot_n, d_rotstep_ch, d_rotstep_n;
     DevBuf d_Y, d_Yn, d_P, d_Pt, d_Q, d_mmse, d_atan, d_aclo, d_achi;
     DevBuf d_le_hdr, d_le_whiten, d_le_index, d_winbits;
-    DevBuf d_pfb_taps_ch, d_pfb_tw, d_binpos_ch, d_binnat_ch, d_rho_ch, d_krot_ch, d_b2map_fused, d_b2map_fused_wide, d_b2map_ch, d_b2map_noise, d_b2map_f320, d_dftw_ch, d_dftw_n;
+    DevBuf d_pfb_taps_ch, d_pfb_tw, d_binpos_ch, d_binnat_ch, d_rho_ch, d_krot_ch, d_b2map_fused, d_b2map_fused_wide, d_b2map_ch, d_b2map_noise, d_b2map_f320, d_dftw_ch, d_dftw_n, d_arows_ch, d_arows_n;
     DevBuf d_pfb_taps_n, d_binpos_n, d_krot_n, d_h3, d_w, d_taps_s1, d_rot_s1, d_rotstep_s1, d_prof, d_pcol, d_wh18;
     LaunchShape shape_s1;
     bool noise_pfb = false;
     bool pfb_small = false, noise_small = false;   // small-M polyphase banks (rates below 100 Msps)
+    bool pfb_g = false, noise_g = false;             // ... of them, the general-M kernel with the DFT on the matrix pipe (pfbg.hip.h)
     bool fuse_noise = false;         // noise stage 1 rides on the channel bank's staged input
     bool use_dcol = false;          // 100-bin bank: also writes the tile-blocked channel-major copy the tail reads
     long long zstride = 0;
@@ -219,7 +220,7 @@ struct btgpu_handle {
         DevBuf *all[] = {&d_in, &d_in_b, &d_taps_ch, &d_taps_n, &d_rot_ch, &d_rot_n, &d_rotstep_ch, &d_rotstep_n,
                          &d_Y, &d_Yn, &d_P, &d_Pt, &d_Q, &d_mmse, &d_atan, &d_aclo, &d_achi,
                          &d_le_hdr, &d_le_whiten, &d_le_index, &d_winbits,
-                         &d_pfb_taps_ch, &d_pfb_tw, &d_binpos_ch, &d_binnat_ch, &d_rho_ch, &d_krot_ch, &d_b2map_fused, &d_b2map_fused_wide, &d_b2map_ch, &d_b2map_noise, &d_b2map_f320, &d_dftw_ch, &d_dftw_n,
+                         &d_pfb_taps_ch, &d_pfb_tw, &d_binpos_ch, &d_binnat_ch, &d_rho_ch, &d_krot_ch, &d_b2map_fused, &d_b2map_fused_wide, &d_b2map_ch, &d_b2map_noise, &d_b2map_f320, &d_dftw_ch, &d_dftw_n, &d_arows_ch, &d_arows_n,
                          &d_pfb_taps_n, &d_binpos_n, &d_krot_n, &d_h3, &d_w, &d_taps_s1, &d_rot_s1, &d_rotstep_s1, &d_prof, &d_pcol, &d_wh18, &d_tapsA, &d_tapsD};
         for (DevBuf *b : all) if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
         for (TailCtx &t : tc) {
@@ -328,7 +329,20 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
     bool fused_m = false;                                       // small-M banks: stage 1 ran inside the channel bank's kernel
 
     // ---- channel bank -> demodulated stream d[g][nch] + |Y|^2 tile sums (polyphase) or block sums P, Pt (direct) ----
-    if (use_pfb && pfb_small) {
+    // the general-M bank (pfbg.hip.h): more than 48 KiB of dynamic LDS is asked for here, once per kernel launched, as below
+    auto Lg = [&](void (*kern)(PfbgParams), int grid, int threads, size_t lds, const PfbgParams &p) {
+        if (lds > 48 * 1024 && std::find(lds_opted.begin(), lds_opted.end(), (const void *)kern) == lds_opted.end()) {
+            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(lds, 64 * 1024));
+            lds_opted.push_back((const void *)kern);
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)threads), lds, st, p);
+    };
+    if (use_pfb && pfb_g) {
+        BankBuffers bb = bank_buffers(d_x, t);
+        ntiles = launch_channel_bank_g(des, fp, bb, (const float4 *)d_arows_ch.p, x_len, w0, G, Lg, s16);
+        tiles_per_block = ops / pfbm_tile(fp.channel.M); tail_tiles = des.tail / pfbm_tile(fp.channel.M);
+        HIPCHK(this, mark(1, st));
+    } else if (use_pfb && pfb_small) {
         BankBuffers bb = bank_buffers(d_x, t);
         auto L = [&](void (*kern)(PfbmParams), int grid, int threads, size_t lds, const PfbmParams &p) {
             hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)threads), lds, st, p);
@@ -399,6 +413,9 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
                 hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)threads), lds, st, p);
             };
             launch_noise_bank(des, fp, bb, x_len, w0, S, L, s16);
+        } else if (noise_g) {
+            BankBuffers bb = bank_buffers(d_x, t);
+            launch_noise_bank_g(des, fp, bb, (const float4 *)d_arows_n.p, x_len, w0, S, Lg, s16);
         } else if (noise_small) {
             BankBuffers bb = bank_buffers(d_x, t);
             auto L = [&](void (*kern)(PfbmParams), int grid, int threads, size_t lds, const PfbmParams &p) {
@@ -991,13 +1008,24 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         const bool pfbm_ok = fp->channel.available && fp->channel.M >= 4 && fp->channel.M < kPfbM &&
                              h->des.outs_per_slot % pfbm_tile(fp->channel.M) == 0 &&
                              pfbm_lds_bytes(fp->channel.M, fp->channel.D, fp->channel.Q, nch0, true) <= lds_cap;
-        const bool pfb_ok = !h->des.segmented && (frc == BTGPU_OK || frc == BTGPU_EUNSUPPORTED) && (pfb100_ok || pfbm_ok);
+        // ... and where that bank's DFT table does not fit the LDS (66 .. 98 Msps): the general-M bank, DFT on the matrix pipe
+        // (pfbg.hip.h).  BTGPU_BANK_FORM=mfma (A/B timing only) runs it also where pfbm_kernel fits, from 52 Msps up.
+        const bool pfbg_ok = pfbg_serves(fp->channel, nch0) && fp->channel.M < kPfbM && h->des.outs_per_slot % pfbm_tile(fp->channel.M) == 0 &&
+                             pfbg_lds_bytes(fp->channel.M, fp->channel.D, fp->channel.Q, true, fp->channel.real_taps) <= lds_cap;
+        const bool pfbg_asked = getenv("BTGPU_BANK_FORM") && std::strcmp(getenv("BTGPU_BANK_FORM"), "mfma") == 0 && fp->channel.M >= 52;
+        const bool pfbg_runs = pfbg_ok && (!pfbm_ok || pfbg_asked);
+        const bool pfb_ok = !h->des.segmented && (frc == BTGPU_OK || frc == BTGPU_EUNSUPPORTED) && (pfb100_ok || pfbm_ok || pfbg_ok);
         const bool noise_pfb_ok = fp->noise.available && fp->noise.pfb.available && fp->noise.pfb.M == kPfbM &&
                                   fp->noise.pfb.Q == 15 && fp->noise.pfb.S == 5;
         const bool noise_small_ok = fp->noise.available && fp->noise.pfb.available && fp->noise.pfb.M >= 4 && fp->noise.pfb.M < kPfbM &&
                                     pfbm_lds_bytes(fp->noise.pfb.M, fp->noise.pfb.D, fp->noise.pfb.Q, nch0, false) <= lds_cap;
-        const bool staged_ok = !h->des.segmented && fp->noise.available &&
-                               (noise_pfb_ok || noise_small_ok || pick_shape(fp->noise.R, fp->noise.direct.ntp, h->shape_s1));
+        // stage 1 as it was served so far, else the general-M bank's noise form
+        const bool staged_old = !h->des.segmented && fp->noise.available &&
+                                (noise_pfb_ok || noise_small_ok || pick_shape(fp->noise.R, fp->noise.direct.ntp, h->shape_s1));
+        const bool noise_g_ok = !h->des.segmented && fp->noise.available && !staged_old && pfbg_serves(fp->noise.pfb, nch0) &&
+                                fp->noise.pfb.M < kPfbM &&
+                                pfbg_lds_bytes(fp->noise.pfb.M, fp->noise.pfb.D, fp->noise.pfb.Q, false, false) <= lds_cap;
+        const bool staged_ok = staged_old || noise_g_ok;
         h->noise_pfb = noise_pfb_ok;
         h->noise_small = noise_small_ok && !getenv("BTGPU_NO_PFBM_NOISE");
         h->fuse_noise = false;
@@ -1009,14 +1037,19 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
             if (sq == BTGPU_SQUELCH_AUTO) sq = BTGPU_SQUELCH_DIRECT;
         }
         if (ch == BTGPU_CHANNELIZER_AUTO) ch = pfb_ok ? BTGPU_CHANNELIZER_POLYPHASE : BTGPU_CHANNELIZER_DIRECT;
-        if (sq == BTGPU_SQUELCH_AUTO) sq = staged_ok ? BTGPU_SQUELCH_STAGED : BTGPU_SQUELCH_DIRECT;
+        // (the new noise form under AUTO: beside a polyphase channel bank from 66 Msps up; 52 .. 64 Msps keep DIRECT.  At 66 Msps
+        // pfbm_kernel's channel form still fits -- 97 376 of 98 304 bytes -- and keeps serving it)
+        if (sq == BTGPU_SQUELCH_AUTO)
+            sq = (staged_old || (noise_g_ok && ch == BTGPU_CHANNELIZER_POLYPHASE && fp->noise.pfb.M >= 66)) ? BTGPU_SQUELCH_STAGED : BTGPU_SQUELCH_DIRECT;
         if ((ch == BTGPU_CHANNELIZER_POLYPHASE && !pfb_ok) || (sq == BTGPU_SQUELCH_STAGED && !staged_ok) ||
             (ch != BTGPU_CHANNELIZER_POLYPHASE && ch != BTGPU_CHANNELIZER_DIRECT) ||
             (sq != BTGPU_SQUELCH_STAGED && sq != BTGPU_SQUELCH_DIRECT)) { delete h; return BTGPU_EUNSUPPORTED; }
         h->use_pfb = ch == BTGPU_CHANNELIZER_POLYPHASE;
         h->pfb_small = h->use_pfb && !pfb100_ok;
+        h->pfb_g = h->pfb_small && pfbg_runs;
         h->use_dcol = h->use_pfb && !h->pfb_small && getenv("BTGPU_NO_DCOL") == nullptr;   // (the knob: A/B timing only)
         h->use_staged = sq == BTGPU_SQUELCH_STAGED;
+        h->noise_g = h->use_staged && noise_g_ok;
         h->keep_Y = !h->use_pfb || (cfg->flags & BTGPU_FLAG_DEBUG_Y);
         h->margin = h->use_staged ? kNoiseMargin : 0;
         h->fuse_noise = h->use_pfb && h->use_staged && noise_pfb_ok && fp->channel.D == 50 && fp->noise.R == 250 &&
@@ -1176,7 +1209,8 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         const PfbBank &b = h->fp.channel;
         h->ntiles_max = (int)((G + pfbm_tile(b.M) - 1) / pfbm_tile(b.M));
         TRY(h->upload(h->d_pfb_taps_ch, b.taps.data(), b.taps.size() * sizeof(float)));
-        TRY(h->upload(h->d_dftw_ch, b.dftw.data(), b.dftw.size() * sizeof(float)));
+        if (h->pfb_g) { const std::vector<float> ar = pack_dft_rows(b); TRY(h->upload(h->d_arows_ch, ar.data(), ar.size() * sizeof(float))); }
+        else TRY(h->upload(h->d_dftw_ch, b.dftw.data(), b.dftw.size() * sizeof(float)));
         TRY(h->upload(h->d_rho_ch, b.rho.data(), b.rho.size() * sizeof(float)));
         TRY(h->upload(h->d_krot_ch, b.krot.data(), b.krot.size() * sizeof(float)));
     } else if (h->use_pfb) {
@@ -1213,6 +1247,11 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
                 if (mn.empty()) return fail(BTGPU_EUNSUPPORTED);
                 TRY(h->upload(h->d_b2map_noise, mn.data(), mn.size() * sizeof(uint16_t)));
             }
+            TRY(h->upload(h->d_krot_n, ns.pfb.krot.data(), ns.pfb.krot.size() * sizeof(float)));
+        } else if (h->noise_g) {
+            const std::vector<float> ar = pack_dft_rows(ns.pfb);
+            TRY(h->upload(h->d_arows_n, ar.data(), ar.size() * sizeof(float)));
+            TRY(h->upload(h->d_pfb_taps_n, ns.pfb.taps.data(), ns.pfb.taps.size() * sizeof(float)));
             TRY(h->upload(h->d_krot_n, ns.pfb.krot.data(), ns.pfb.krot.size() * sizeof(float)));
         } else if (h->noise_small) {
             TRY(h->upload(h->d_pfb_taps_n, ns.pfb.taps.data(), ns.pfb.taps.size() * sizeof(float)));

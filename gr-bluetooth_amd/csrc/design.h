@@ -117,6 +117,12 @@ std::vector<uint16_t> make_dft_pass2_map(int rows, int lanes, int sweeps);
 // tap-major: what the small-M kernel stages through LDS.)
 std::vector<float> pack_branch_major(const PfbBank &b);
 
+// The general-M kernel's A operand (pfbg.hip.h): the bank's DFT b.dftw as the real matrix [[W_re, -W_im], [W_im, W_re]], rows =
+// (channel, re / im), K = the 2 M interleaved floats of a branch-output row, in the order the matrix instruction's lanes take
+// them: [wave of 5][group g of ceil(2 M / 8)][lane of 64][step s of 4] = A[row 32 wave + lane % 32][float 8 g + 4 (lane / 32) + s],
+// zero for the rows past the last channel and the floats past 2 M.
+std::vector<float> pack_dft_rows(const PfbBank &b);
+
 struct NoiseStage {
     bool available = false;
     int R = 0;                          // stage-1 hop = 5 * decimation

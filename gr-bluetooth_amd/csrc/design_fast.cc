@@ -186,6 +186,25 @@ std::vector<float> pack_branch_major(const PfbBank &b)
     return out;
 }
 
+std::vector<float> pack_dft_rows(const PfbBank &b)
+{
+    const int M = b.M, nch = M > 0 ? (int)(b.dftw.size() / ((size_t)2 * M)) : 0;
+    const int ng = (2 * M + 7) / 8, waves = 5;
+    std::vector<float> out((size_t)waves * ng * 64 * 4, 0.f);
+    for (int w = 0; w < waves; w++)
+        for (int g = 0; g < ng; g++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int s = 0; s < 4; s++) {
+                    const int row = 32 * w + (lane & 31), c = row >> 1, im_row = row & 1;
+                    const int f = 8 * g + 4 * (lane >> 5) + s, p = f >> 1, im_in = f & 1;
+                    if (c >= nch || p >= M) continue;
+                    const float wr = b.dftw[((size_t)p * nch + c) * 2], wi = b.dftw[((size_t)p * nch + c) * 2 + 1];
+                    // (Y_re, Y_im) = [[W_re, -W_im], [W_im, W_re]] (u_re, u_im)
+                    out[(((size_t)w * ng + g) * 64 + lane) * 4 + s] = im_row ? (im_in ? wr : wi) : (im_in ? -wi : wr);
+                }
+    return out;
+}
+
 std::vector<uint16_t> make_dft_pass2_map(int rows, int lanes, int sweeps)
 {
     // residue classes of the tasks

@@ -9,6 +9,7 @@
 #include "pfb100.hip.h"
 #include "pfb100f.hip.h"
 #include "pfbm.hip.h"
+#include "pfbg.hip.h"
 #include "exact.hip.h"
 #include "exact_dense.hip.h"
 
@@ -44,6 +45,10 @@ BTGPU_S16_KERNEL(pfbm_kernel_s16<false, true, 0, 0, false, false>(PfbmParams))
 BTGPU_S16_KERNEL(pfbm_kernel_s16<false, false, 8, 15, true, false>(PfbmParams))
 BTGPU_S16_KERNEL(pfbm_kernel_s16<false, false, 8, 15, false, false>(PfbmParams))
 BTGPU_S16_KERNEL(pfbm_kernel_s16<false, false, 0, 0, false, false>(PfbmParams))
+// general-M bank, DFT on the matrix pipe (launch_channel_bank_g, launch_noise_bank_g)
+BTGPU_S16_KERNEL(pfbg_kernel_s16<true, true>(PfbgParams))
+BTGPU_S16_KERNEL(pfbg_kernel_s16<false, true>(PfbgParams))
+BTGPU_S16_KERNEL(pfbg_kernel_s16<false, false>(PfbgParams))
 // exact rows: every decimation exact_rows_pick serves
 #define BTGPU_S16_EX(n) BTGPU_S16_KERNEL(exact_rows_kernel_s16<n>(ExactParams, const float2 *))
 BTGPU_S16_EX(2) BTGPU_S16_EX(3) BTGPU_S16_EX(4) BTGPU_S16_EX(5) BTGPU_S16_EX(6) BTGPU_S16_EX(7) BTGPU_S16_EX(8) BTGPU_S16_EX(9)

@@ -84,7 +84,7 @@ extern "C" {
                                            reference's in slot, channel, kind, offset, LAP and ac_errors, and the symbols handed to the
                                            host layer are the reference's to the end of each packet; with this flag ~1e-4 .. 2e-2 of the
                                            records (by traffic) come out a symbol apart or on one side only (the round-3 behaviour).
-                                           Exact rows are served at every rate the polyphase channelizer is: 4 .. 64 and 100 Msps */
+                                           Exact rows are served at every rate the polyphase channelizer is: 4 .. 100 Msps, even */
 
 #define BTGPU_FLAG_EXACT_PAYLOAD 0x200   /* accepted; ALWAYS ON since round 6.  The symbols a record hands to the host layer are the reference's
                                            own arithmetic to the END OF THE PACKET: a packet's air time is busy, so its rows are exact rows
@@ -96,7 +96,7 @@ extern "C" {
                                            nsym and the records born from noise included, equals the CPU reference's with the bit-exact
                                            channelizer's (the squelch figure stays the staged filter's: SNR within 3.4e-6 dB).  ~8 Gsamples/s
                                            at 79 channels / 100 Msps instead of ~30.  Honoured at every rate the
-                                           polyphase channelizer serves: 4 .. 64 Msps (52 .. 64 in the dense form only) and 100 Msps */
+                                           polyphase channelizer serves: 4 .. 100 Msps, even (52 .. 98 in the dense form only) */
 
 #define BTGPU_FLAG_EXACT_DENSE 0x800     /* exact rows in their DENSE form (csrc/exact_dense.hip.h: 16 channels per matrix row block, the decimation a
                                            run-time argument) also where the tile-sparse form exists.  The same bits in every row either way; the
