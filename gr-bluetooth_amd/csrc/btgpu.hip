@@ -78,8 +78,8 @@ struct btgpu_handle {
     static constexpr int kCtx = kCtxMax; // in-flight batches (BTGPU_FLAG_ASYNC): front(n+2) | post(n+1) | tail(n)
     struct TailCtx {                 // per in-flight batch: everything the front writes and the post / tail stages read
         DevBuf d_winlen, d_hits, d_hitcount, d_fin, d_winfin, d_symbits, d_hdr;
-        DevBuf d_d;                           // demodulated stream of the batch
-        DevBuf d_dcol;                        // 100-bin bank: the same stream tile by tile channel-major [tile][80][25], what finish_kernel reads
+        DevBuf d_d;                           // demodulated stream of the batch, time-major [G][drow] -- not allocated where d_dcol is the stream
+        DevBuf d_dcol;                        // 100-bin bank: the stream tile by tile channel-major [tile][80][25], the only one of such a handle
         DevBuf d_ptile, d_phead;              // polyphase banks: |Y|^2 tile sums (-> block_sum_kernel on the post stream)
         DevBuf d_pfine;                       // small-M F8 bank: |Y|^2 sums per 25 instants (the exact stage's burst scan)
         DevBuf d_Z;                           // staged squelch: stage-1 output (-> noise_stage2_kernel on the post stream)
@@ -177,7 +177,7 @@ struct btgpu_handle {
     bool pfb_small = false, noise_small = false;   // small-M polyphase banks (rates below 100 Msps)
     bool pfb_g = false, noise_g = false;             // ... of them, the general-M kernel with the DFT on the matrix pipe (pfbg.hip.h)
     bool fuse_noise = false;         // noise stage 1 rides on the channel bank's staged input
-    bool use_dcol = false;          // 100-bin bank: also writes the tile-blocked channel-major copy the tail reads
+    bool use_dcol = false;          // 100-bin bank: the demodulated stream is tile-blocked (d_dcol) and there is no time-major d_d; every consumer reads it
     long long zstride = 0;
     int ntiles_max = 0;
     LaunchShape shape_ch, shape_n;
@@ -203,8 +203,10 @@ struct btgpu_handle {
             return BTGPU_ENOMEM;
         }
         b.bytes = bytes;
+        dev_bytes += bytes;
         return BTGPU_OK;
     }
+    size_t dev_bytes = 0;           // device memory this handle has allocated (BTGPU_VERBOSE)
     int upload(DevBuf &b, const void *src, size_t bytes)
     {
         int rc = alloc(b, bytes);
@@ -545,7 +547,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
         auto launch_window = [&](auto lay) {
             using LAY = decltype(lay);
             hipLaunchKernelGGL(window_kernel<LAY>, dim3((S + LAY::kSlots - 1) / LAY::kSlots), dim3(kWinThreads), 0, ps, p,
-                               (const float *)d_d.p, G,
+                               (const float *)(LAY::kTiled ? t.d_dcol.p : d_d.p), G,
                                (const double *)d_P.p, (const double *)d_Pt.p, (const double *)d_Q.p,
                                (const float *)d_mmse.p, (const uint64_t *)d_aclo.p, (const uint32_t *)d_achi.p,
                                (double *)t.d_eon.p, (double *)t.d_eoff.p, (double *)t.d_snr.p, (int *)d_winlen.p,
@@ -558,7 +560,8 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
         // (BTGPU_WIN_ROWS=29: 29 rows per chunk = 39.8 KB of LDS, four workgroups per CU instead of three, for A/B -- no faster)
         static const bool win29 = [] { const char *e = getenv("BTGPU_WIN_ROWS"); return e && atoi(e) == 29; }();
         // (deferred squelch: the 39.8 KB layout -- three window workgroups leave a CU 40 KB for a stage-2 workgroup beside them)
-        if (drow == 80 && (win29 || deferred)) launch_window(WinLayout<3, 96, 20, kWinRowsSmall>{});
+        if (use_dcol) launch_window(WinLayoutTiled{});          // the tile-blocked stream: its own staging form (38.7 KB of LDS: beside a stage-2 workgroup too)
+        else if (drow == 80 && (win29 || deferred)) launch_window(WinLayout<3, 96, 20, kWinRowsSmall>{});
         else if (drow == 80) launch_window(WinLayout<3, 96, 20>{});
         else if (drow == 40) launch_window(WinLayout<6, 40, 10>{});
         else if (drow == 20) launch_window(WinLayout<12, 20, 5>{});
@@ -1047,7 +1050,9 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         h->use_pfb = ch == BTGPU_CHANNELIZER_POLYPHASE;
         h->pfb_small = h->use_pfb && !pfb100_ok;
         h->pfb_g = h->pfb_small && pfbg_runs;
-        h->use_dcol = h->use_pfb && !h->pfb_small && getenv("BTGPU_NO_DCOL") == nullptr;   // (the knob: A/B timing only)
+        // BTGPU_NO_DCOL=1: the 100-bin bank writes the time-major stream instead and every consumer reads that (A/B timing, and the
+        // reference layout of tests/test_gpu_dcol_stream.py)
+        h->use_dcol = h->use_pfb && !h->pfb_small && getenv("BTGPU_NO_DCOL") == nullptr;
         h->use_staged = sq == BTGPU_SQUELCH_STAGED;
         h->noise_g = h->use_staged && noise_g_ok;
         h->keep_Y = !h->use_pfb || (cfg->flags & BTGPU_FLAG_DEBUG_Y);
@@ -1336,7 +1341,7 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
             TRY(h->alloc(t.d_dxt, ((size_t)nps * kVerRows + 64) * h->drow * sizeof(float)));
             TRY(h->alloc(t.d_winbits_v, (size_t)(nps + 1) * kBitWords * kWinThreads * sizeof(uint32_t)));
         }
-        TRY(h->alloc(t.d_d, (size_t)h->drow * (h->ystride + 64) * sizeof(float)));   // [G][drow], time-major
+        if (!h->use_dcol) TRY(h->alloc(t.d_d, (size_t)h->drow * (h->ystride + 64) * sizeof(float)));   // [G][drow], time-major
         if (h->use_dcol) TRY(h->alloc(t.d_dcol, (size_t)((h->ystride + 64) / (kBankNT - 1) + 2) * 80 * (kBankNT - 1) * sizeof(float)));
         if (h->want_hdrs) TRY(h->alloc(t.d_hdr, (size_t)h->max_hits * sizeof(HeaderRec)));
         if (h->want_syms) {
@@ -1410,7 +1415,8 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, false, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     h->pre.assign((size_t)h->margin * 2, 0.f);
     if (getenv("BTGPU_VERBOSE"))
-        fprintf(stderr, "btgpu_create: %d contexts, d=%p Z=%p ptile=%p\n", h->nctx, h->tc[0].d_d.p, h->tc[0].d_Z.p, h->tc[0].d_ptile.p);
+        fprintf(stderr, "btgpu_create: %d contexts, d=%p Z=%p ptile=%p; device memory %zu bytes, per context: time-major stream %zu, tile-blocked stream %zu\n",
+                h->nctx, h->tc[0].d_d.p, h->tc[0].d_Z.p, h->tc[0].d_ptile.p, h->dev_bytes, h->tc[0].d_d.bytes, h->tc[0].d_dcol.bytes);
 
     h->carry.assign((size_t)(d.history - 1) * 2, 0.f);   // GNU Radio pre-fills history()-1 zeros [EXT]
     *out = h;
@@ -1667,6 +1673,18 @@ long btgpu_debug_fetch(btgpu_handle *h, int what, int channel, size_t first, siz
             count = std::min(count, avail - first);
             if (hipSetDevice(h->device) != hipSuccess) return BTGPU_EDEVICE;
             // (the rows as they lie, the channel's column picked on the host: a 2-D copy of 4-byte rows took ~70 ms per call)
+            if (h->use_dcol) {
+                // no time-major stream: the tiles that hold the rows, the channel's run of each picked on the host
+                const size_t t0 = first / 25, t1 = (first + count - 1) / 25;
+                std::vector<float> tiles((t1 - t0 + 1) * (size_t)2000);
+                if (hipMemcpy(tiles.data(), (const float *)h->tc[h->last_ctx].d_dcol.p + t0 * 2000, tiles.size() * sizeof(float),
+                              hipMemcpyDeviceToHost) != hipSuccess) return BTGPU_EDEVICE;
+                for (size_t i = 0; i < count; i++) {
+                    const size_t g = first + i;
+                    ((float *)out)[i] = tiles[(g / 25 - t0) * 2000 + (size_t)c * 25 + g % 25];
+                }
+                return (long)count;
+            }
             std::vector<float> rows(count * (size_t)h->drow);
             if (hipMemcpy(rows.data(), (const float *)h->tc[h->last_ctx].d_d.p + first * h->drow, rows.size() * sizeof(float),
                           hipMemcpyDeviceToHost) != hipSuccess) return BTGPU_EDEVICE;

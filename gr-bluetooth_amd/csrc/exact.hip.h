@@ -245,7 +245,7 @@ __device__ __forceinline__ void exact_rows_body(const ExactParams &p, const floa
             if (row_ok && !(p.dbg & 2)) {
                 const float dv = demod_one(atab, p.gain, y, yp);
                 if (!(p.dbg & 1)) {
-                    drow_p[c] = dv;
+                    if (p.d) drow_p[c] = dv;                   // (uniform: a handle with the tile-blocked stream has no time-major one)
                     if (dcol_p) dcol_p[25 * c] = dv;
                 }
             }

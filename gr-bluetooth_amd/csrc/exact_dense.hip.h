@@ -163,7 +163,7 @@ __device__ __forceinline__ void exact_dense_body(const ExactParams &p, const flo
             }
             __syncthreads();
             // ---- stores, lanes remapped.  d[g][.]: 16 lanes = the block's 16 channels of one row ----
-            {
+            if (p.d) {
                 const int cl = tid & 15, c = kExDenseRows * b + cl;
                 const bool c_ok = c < p.nch && ((mask >> cl) & 1u);
 #pragma unroll

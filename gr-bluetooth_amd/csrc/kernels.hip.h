@@ -425,6 +425,17 @@ struct WinLayout {
     static constexpr int kSlots = NSL, kRowStride = RS, kVecPerRow = NCP4;
     static constexpr int kRows = ROWS;                       // demod rows staged per chunk and slot
     static constexpr int kTileFloats = ROWS * RS + (RS % 32 == 0 ? 16 : 8);
+    static constexpr bool kTiled = false;                    // stages from the time-major stream d[g][4 * NCP4]
+};
+// The window kernel on the 100-bin bank's tile-blocked stream dcol[tile][80][25] (41..80 channels, three slots per workgroup like
+// <3, 96, 20>): the LDS tile is channel-major, a column of kCarry + kTile rows at an odd pitch, and a chunk is one 25-row tile.
+// 3 x 2712 floats = 32.5 KB: what phase 2's tables need; with the interpolator 38.7 KB, four workgroups per CU.
+struct WinLayoutTiled {
+    static constexpr int kSlots = 3, kTile = 25, kCarry = 7, kPitch = 33;
+    static constexpr int kRowStride = 1;                     // consecutive rows of a column are consecutive floats
+    static constexpr int kVecPerRow = 20, kRows = kTile;
+    static constexpr int kTileFloats = 80 * kPitch + 72;
+    static constexpr bool kTiled = true;
 };
 constexpr int kMmseStride = 12;      // floats per interpolator row in LDS: 16-byte slot 3 imu mod 16 instead of
                                      // 2 imu mod 16 (eight classes for the sixteen lanes of a 16-byte read group)
@@ -889,64 +900,9 @@ __global__ __launch_bounds__(kWinThreads) void window_kernel(
     // sliced symbols leave phase 1 through a per-workgroup scratch in HBM ([word][lane], one
     // coalesced store per 32 symbols) and come back into the dead tile for phase 2
     uint32_t *gbits = winbits + (size_t)blockIdx.x * (kBitWords * kWinThreads) + threadIdx.x;
-    const float *mytile = tile + (sl < kWinSlots ? sl : 0) * kTileFloats;
-
-    // Chunk schedule.  A lane leaves a chunk with its input index just past the chunk's last usable
-    // row (index + 8 rows must be staged), so the next chunk always starts kRows - 7 rows further:
-    // the schedule is static and the rows of chunk n + 1 are fetched into registers before the
-    // recursion over chunk n starts -- the HBM round trip hides under the dependent arithmetic.
-    // Every load is unconditional (clamped address): a load under a lane-dependent branch would be
-    // waited for at the end of that branch, nine round trips per chunk.
-    constexpr int kAdv = kRows - 7;
-    constexpr int kVec = kRows * kVecPerRow;                  // float4 per chunk and slot (the used part of the 80-float rows)
-    constexpr int kTot = kVec * kWinSlots;
-    constexpr int kPer = (kTot + kWinThreads - 1) / kWinThreads;
-    float4 v[kPer];
-    // Per-thread constants of the staging copy, computed once: byte offset of element j from the
-    // workgroup's first row (chunk 0) and its float4 index in the LDS tile; bit 31 marks row 0 of a
-    // window (policy Q1: demod_out[0] = 0).  Per chunk an element then costs one add and one clamp.
-    // The clamp only keeps the address inside the stream: rows past the end belong to no window of
-    // this batch (every window's ddc_out rows exist) and are never consumed.
-    constexpr int kRowBytes = kVecPerRow * 16;
-    uint32_t goff[kPer], loff[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; j++) {
-        const int i = (int)threadIdx.x + j * kWinThreads;
-        const int ic = i < kTot ? i : kTot - 1;
-        const int s = ic / kVec, iv = ic - s * kVec;
-        const int r = iv / kVecPerRow, q4 = iv - r * kVecPerRow;
-        goff[j] = (uint32_t)((s * p.rows_per_slot + r) * kRowBytes + q4 * 16);
-        loff[j] = (uint32_t)(s * (kTileFloats / 4) + r * (kWinRowStride / 4) + q4) | (r == 0 ? 0x80000000u : 0u);
-    }
-    const long long wg_row0 = (long long)blockIdx.x * kWinSlots * p.rows_per_slot;
-    const char *wgb = (const char *)(d + (size_t)wg_row0 * (kVecPerRow * 4));
-    const long long span = (d_rows - wg_row0) * kRowBytes - 16;             // last float4 of the stream (d_rows > wg_row0)
-    const uint32_t max_off = span > 0xFFFFFFF0LL ? 0xFFFFFFF0u : (uint32_t)span;
-    auto fetch = [&](int base) {
-        const uint32_t boff = (uint32_t)base * (uint32_t)kRowBytes;
-#pragma unroll
-        for (int j = 0; j < kPer; j++) {
-            const uint32_t o = goff[j] + boff;
-            v[j] = *(const float4 *)(wgb + (o < max_off ? o : max_off));
-        }
-    };
-    int base = 0;
-    fetch(0);
-    for (int it = 0;; it++) {
-#pragma unroll
-        for (int j = 0; j < kPer; j++) {
-            const int i = (int)threadIdx.x + j * kWinThreads;
-            const bool zero = base == 0 && (loff[j] >> 31);
-            const float4 t = make_float4(zero ? 0.f : v[j].x, zero ? 0.f : v[j].y, zero ? 0.f : v[j].z, zero ? 0.f : v[j].w);
-            if (i < kTot) ((float4 *)tile)[loff[j] & 0x7fffffffu] = t;
-        }
-        if (threadIdx.x == 0) s_live[it & 1] = 0;
-        __syncthreads();
-        fetch(base + kAdv);
-        unsigned int lim = (unsigned int)(base + kRows - 8);
-        if (lim > ni - 1) lim = ni - 1;                          // while (ii < ni) of the reference
-        // byte offset of this lane's column in row `base` of the tile (24-bit arithmetic: one v_mad_u32_u24 per symbol)
-        const uint32_t colb = (uint32_t)(((int)(mytile - tile) + c - base * kWinRowStride) * 4);
+    // the recursion over the rows staged in LDS: symbols while the lane's input index is at most `lim`; colb = byte offset of
+    // row 0 of the lane's column in the tile, rows kWinRowStride floats apart (same-thread code of both staging forms)
+    auto recur = [&](unsigned int lim, uint32_t colb) __attribute__((always_inline)) {
         while (ii <= lim && oo < nmax) {
             // interpolate: sum_q T[imu][7-q] * in[ii+q], q ascending
             // mu = x - floor(x) lies in [0, 1] (1.0 when x is a tiny negative number): imu in 0..128, no clamp needed
@@ -1005,10 +961,135 @@ __global__ __launch_bounds__(kWinThreads) void window_kernel(
             }
             oo++;
         }
-        if (oo < nmax && ii < ni) s_live[it & 1] = 1;            // this lane needs another chunk
-        __syncthreads();
-        if (!s_live[it & 1]) break;                              // uniform
-        base += kAdv;
+    };
+    if constexpr (LAY::kTiled) {
+        // ---- staging from the tile-blocked stream dcol[tile][80][25] (the 100-bin bank's only stream) ----
+        // A slot is a whole number of 25-row tiles (the host checks), so chunk `it` of slot s is ONE tile: 2000 contiguous floats,
+        // fetched as they lie (lane = float, the base of every load in scalar registers, the clamp on the tile index: uniform) and
+        // written to LDS channel-major -- column (slot, channel) is a run of kPitch floats, the eight samples of a symbol at
+        // consecutive addresses.  Floats e and e + 1 of a tile are neighbours in LDS too (8 floats further at a channel's end), so
+        // the writes meet no bank twice but for those jumps; the odd pitch spreads the lanes' reads.  A column belongs to its lane
+        // alone: the lane itself moves the chunk's last kCarry = 7 rows to the column's front when it has left the chunk (a lane
+        // leaves with its index within 7 rows of the chunk's end), and itself zeroes row 0 (policy Q1) -- no barrier for either.
+        // Rows past the stream's end (a partial last tile, a slot past S) belong to no window of this batch and are never consumed.
+        static_assert(!VER, "the second run's task stream is time-major");
+        constexpr int kT = LAY::kTile, kCarry = LAY::kCarry, kPitch = LAY::kPitch, kTileElems = 80 * kT;
+        constexpr int kPer = (kTileElems + kWinThreads - 1) / kWinThreads;
+        static_assert(kCarry == 7 && kPitch >= kT + kCarry && (kPitch & 1), "seven rows carried, odd pitch");
+        float v[kWinSlots][kPer];
+        uint32_t eoff[kPer], loff[kPer];                         // float of the tile this thread moves, and its place in a slot's LDS tile
+#pragma unroll
+        for (int j = 0; j < kPer; j++) {
+            const int e = (int)threadIdx.x + j * kWinThreads;
+            const int ec = e < kTileElems ? e : kTileElems - 1;
+            eoff[j] = (uint32_t)ec;
+            loff[j] = (uint32_t)(ec + (kPitch - kT) * (ec / kT) + kCarry);
+        }
+        const long long ntl = (d_rows + kT - 1) / kT;            // tiles of the stream (the last may be a partial one: allocated whole)
+        const long long tps = p.rows_per_slot / kT;
+        auto fetch = [&](int it) {
+#pragma unroll
+            for (int s = 0; s < kWinSlots; s++) {
+                long long tq = ((long long)blockIdx.x * kWinSlots + s) * tps + it;
+                tq = tq < ntl ? tq : ntl - 1;
+                const float *tp = d + (size_t)tq * kTileElems;
+#pragma unroll
+                for (int j = 0; j < kPer; j++) v[s][j] = tp[eoff[j]];
+            }
+        };
+        float *mycol = tile + (sl < kWinSlots ? sl : 0) * kTileFloats + c * kPitch;
+        fetch(0);
+        for (int it = 0;; it++) {
+#pragma unroll
+            for (int s = 0; s < kWinSlots; s++) {
+#pragma unroll
+                for (int j = 0; j < kPer; j++)
+                    if ((j + 1) * kWinThreads <= kTileElems || (int)threadIdx.x + j * kWinThreads < kTileElems) tile[s * kTileFloats + loff[j]] = v[s][j];
+            }
+            if (threadIdx.x == 0) s_live[it & 1] = 0;
+            __syncthreads();
+            fetch(it + 1);
+            if (it == 0 && sl < kWinSlots) mycol[kCarry] = 0.f;    // policy Q1: demod_out[0] = 0
+            const int base = it * kT;
+            unsigned int lim = (unsigned int)(base + kT - 8);
+            if (lim > ni - 1) lim = ni - 1;                          // while (ii < ni) of the reference
+            recur(lim, (uint32_t)(((int)(mycol - tile) + kCarry - base) * 4));
+            if (oo < nmax && ii < ni) s_live[it & 1] = 1;            // this lane needs another chunk
+            if (sl < kWinSlots) {
+                float t[kCarry];
+#pragma unroll
+                for (int q = 0; q < kCarry; q++) t[q] = mycol[kT + q];
+#pragma unroll
+                for (int q = 0; q < kCarry; q++) mycol[q] = t[q];
+            }
+            __syncthreads();
+            if (!s_live[it & 1]) break;                              // uniform
+        }
+    } else {
+        const float *mytile = tile + (sl < kWinSlots ? sl : 0) * kTileFloats;
+
+        // Chunk schedule.  A lane leaves a chunk with its input index just past the chunk's last usable
+        // row (index + 8 rows must be staged), so the next chunk always starts kRows - 7 rows further:
+        // the schedule is static and the rows of chunk n + 1 are fetched into registers before the
+        // recursion over chunk n starts -- the HBM round trip hides under the dependent arithmetic.
+        // Every load is unconditional (clamped address): a load under a lane-dependent branch would be
+        // waited for at the end of that branch, nine round trips per chunk.
+        constexpr int kAdv = kRows - 7;
+        constexpr int kVec = kRows * kVecPerRow;                  // float4 per chunk and slot (the used part of the 80-float rows)
+        constexpr int kTot = kVec * kWinSlots;
+        constexpr int kPer = (kTot + kWinThreads - 1) / kWinThreads;
+        float4 v[kPer];
+        // Per-thread constants of the staging copy, computed once: byte offset of element j from the
+        // workgroup's first row (chunk 0) and its float4 index in the LDS tile; bit 31 marks row 0 of a
+        // window (policy Q1: demod_out[0] = 0).  Per chunk an element then costs one add and one clamp.
+        // The clamp only keeps the address inside the stream: rows past the end belong to no window of
+        // this batch (every window's ddc_out rows exist) and are never consumed.
+        constexpr int kRowBytes = kVecPerRow * 16;
+        uint32_t goff[kPer], loff[kPer];
+    #pragma unroll
+        for (int j = 0; j < kPer; j++) {
+            const int i = (int)threadIdx.x + j * kWinThreads;
+            const int ic = i < kTot ? i : kTot - 1;
+            const int s = ic / kVec, iv = ic - s * kVec;
+            const int r = iv / kVecPerRow, q4 = iv - r * kVecPerRow;
+            goff[j] = (uint32_t)((s * p.rows_per_slot + r) * kRowBytes + q4 * 16);
+            loff[j] = (uint32_t)(s * (kTileFloats / 4) + r * (kWinRowStride / 4) + q4) | (r == 0 ? 0x80000000u : 0u);
+        }
+        const long long wg_row0 = (long long)blockIdx.x * kWinSlots * p.rows_per_slot;
+        const char *wgb = (const char *)(d + (size_t)wg_row0 * (kVecPerRow * 4));
+        const long long span = (d_rows - wg_row0) * kRowBytes - 16;             // last float4 of the stream (d_rows > wg_row0)
+        const uint32_t max_off = span > 0xFFFFFFF0LL ? 0xFFFFFFF0u : (uint32_t)span;
+        auto fetch = [&](int base) {
+            const uint32_t boff = (uint32_t)base * (uint32_t)kRowBytes;
+    #pragma unroll
+            for (int j = 0; j < kPer; j++) {
+                const uint32_t o = goff[j] + boff;
+                v[j] = *(const float4 *)(wgb + (o < max_off ? o : max_off));
+            }
+        };
+        int base = 0;
+        fetch(0);
+        for (int it = 0;; it++) {
+    #pragma unroll
+            for (int j = 0; j < kPer; j++) {
+                const int i = (int)threadIdx.x + j * kWinThreads;
+                const bool zero = base == 0 && (loff[j] >> 31);
+                const float4 t = make_float4(zero ? 0.f : v[j].x, zero ? 0.f : v[j].y, zero ? 0.f : v[j].z, zero ? 0.f : v[j].w);
+                if (i < kTot) ((float4 *)tile)[loff[j] & 0x7fffffffu] = t;
+            }
+            if (threadIdx.x == 0) s_live[it & 1] = 0;
+            __syncthreads();
+            fetch(base + kAdv);
+            unsigned int lim = (unsigned int)(base + kRows - 8);
+            if (lim > ni - 1) lim = ni - 1;                          // while (ii < ni) of the reference
+            // byte offset of this lane's column in row `base` of the tile (24-bit arithmetic: one v_mad_u32_u24 per symbol)
+            const uint32_t colb = (uint32_t)(((int)(mytile - tile) + c - base * kWinRowStride) * 4);
+            recur(lim, colb);
+            if (oo < nmax && ii < ni) s_live[it & 1] = 1;            // this lane needs another chunk
+            __syncthreads();
+            if (!s_live[it & 1]) break;                              // uniform
+            base += kAdv;
+        }
     }
     if (oo & 31) gbits[(oo >> 5) * kWinThreads] = sym_word(cur, oo & 31);
     if (p.dbg_stop == 2) return;

@@ -646,7 +646,7 @@ __device__ __forceinline__ void pfb100_body(const PfbParams &p)
             const long long g1 = t0 + 1;                             // first owned instant
             const long long rows = p.T - g1 < TT ? p.T - g1 : TT;    // ... inside the stream
             float4 *dst = (float4 *)(p.d + (size_t)g1 * 80);
-            if (!(p.dbg & 2))
+            if (p.d && !(p.dbg & 2))                                 // (p.d == nullptr: no time-major copy)
                 for (int i = l; i < (int)rows * 20; i += NTH) dst[i] = ((const float4 *)s_d)[i];
             if (p.dcol && !(p.dbg & 2)) {
                 // the whole tile, instants past the stream included (never read): 80 TT floats = TT * 20 pieces

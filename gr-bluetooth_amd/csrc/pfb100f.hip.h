@@ -275,6 +275,7 @@ __device__ __forceinline__ void pfb100f_body(const PfbParams &p)
     };
     // angle tiles + tile sums of a finished tile -> HBM (reads the epilogue's LDS tiles: call between its barrier
     // and the next barrier, before phase A of the following tile writes the DFT rows again)
+    const bool wd = p.d != nullptr;                              // uniform: the time-major copy is wanted (nullptr: dcol is the only stream)
     auto copy_out = [&](int tile, int l) {
         const long long g1 = (long long)tile * TT;                               // first owned instant
         const long long rows = p.T - g1 < TT ? p.T - g1 : TT;                    // ... inside the stream
@@ -285,13 +286,15 @@ __device__ __forceinline__ void pfb100f_body(const PfbParams &p)
         // with a run-time trip count would pay an LDS round trip in front of every store)
         static_assert(TT * 20 <= 2 * NTH, "two pieces per lane");
         const int n_d = (int)rows * 20, i1 = l + NTH;
-        const f4 a0 = ((const f4 *)s_d)[l], a1 = ((const f4 *)s_d)[i1 < TT * 20 ? i1 : l];
         const f4 b0 = ((const f4 *)s_dc)[l], b1 = ((const f4 *)s_dc)[i1 < TT * 20 ? i1 : l];
         // (uniform base + 32-bit lane offset: the store takes the base from scalar registers, no 64-bit lane arithmetic)
-        char *dst = (char *)(p.d + (size_t)g1 * 80);
         const unsigned o0 = (unsigned)l * 16u, o1 = (unsigned)i1 * 16u;
-        if (l < n_d) __builtin_nontemporal_store(a0, (f4 *)(dst + o0));
-        if (i1 < n_d) __builtin_nontemporal_store(a1, (f4 *)(dst + o1));
+        if (wd) {                                                                // (uniform)
+            const f4 a0 = ((const f4 *)s_d)[l], a1 = ((const f4 *)s_d)[i1 < TT * 20 ? i1 : l];
+            char *dst = (char *)(p.d + (size_t)g1 * 80);
+            if (l < n_d) __builtin_nontemporal_store(a0, (f4 *)(dst + o0));
+            if (i1 < n_d) __builtin_nontemporal_store(a1, (f4 *)(dst + o1));
+        }
         if (p.dcol) {
             char *dc = (char *)(p.dcol + (size_t)tile * (80 * TT));
             if (l < TT * 20) __builtin_nontemporal_store(b0, (f4 *)(dc + o0));
@@ -533,7 +536,7 @@ __device__ __forceinline__ void pfb100f_body(const PfbParams &p)
                     pr = fmaf(by, yc_.y, pr);
                     pi = fmaf(-by, yc_.x, pi);
                     const float ang = demod_poly_pz(kc, c5, pr, pi);
-                    drow[k * 80] = ang;
+                    if (wd) drow[k * 80] = ang;
                     dcolp[k] = ang;
                 };
                 constexpr int LAST = TT - (CH - 1) * RUN;        // instants of the last run
@@ -552,8 +555,8 @@ __device__ __forceinline__ void pfb100f_body(const PfbParams &p)
                         pi0 = fmaf(-by0, y1.x, pi0); pi1 = fmaf(-by1, y2.x, pi1);
                         float a0, a1;
                         demod_poly_pz2(kc, c5, pr0, pi0, pr1, pi1, a0, a1);
-                        drow[k * 80] = a0; dcolp[k] = a0;
-                        drow[(k + 1) * 80] = a1; dcolp[k + 1] = a1;
+                        if (wd) { drow[k * 80] = a0; drow[(k + 1) * 80] = a1; }
+                        dcolp[k] = a0; dcolp[k + 1] = a1;
                     };
                     // (LAST and RUN odd: pairs (0,1) .. (LAST-3, LAST-2); then LAST-1 alone, or (LAST-1, LAST) .. and RUN-1 alone)
 #pragma unroll
@@ -602,7 +605,7 @@ __device__ __forceinline__ void pfb100f_body(const PfbParams &p)
                     if (tl0 + k - 1 < hr) head += m;
                     const cf pq = ybr.xx * ya + ybr.yy * mk(ya.y, -ya.x);                       // Y[t] conj(Y[t-1]) rho
                     const float ang = demod_poly(kc, pq.x, pq.y);
-                    drow[k * 80] = ang;
+                    if (wd) drow[k * 80] = ang;
                     dcolp[k] = ang;
                 }
                 yb = ya; ya = yn;
