@@ -36,6 +36,8 @@ FLAG_EXACT_PAYLOAD = 512  # exported symbols exact to the end of the packet (inc
 FLAG_EXACT_ALL = 1024     # no selection: every row of every channel exact (include/btgpu.h)
 FLAG_EXACT_DENSE = 2048   # exact rows in the dense form also where the sparse one exists (include/btgpu.h)
 EXACT_NONE, EXACT_SPARSE, EXACT_DENSE = 0, 1, 2     # exact_form()
+FLAG_DIRECT_MFMA = 4096  # the direct-form banks on the matrix pipe (include/btgpu.h)
+DIRECT_VALU, DIRECT_MFMA = 0, 1                     # direct_form()
 KIND_AC, KIND_AA = 0, 1
 
 
@@ -87,7 +89,7 @@ EXPORTS = ["btgpu_design_query", "btgpu_acgen", "btgpu_filter_taps", "btgpu_stre
            "btgpu_hopseq_init_candidates", "btgpu_hopseq_winnow", "btgpu_hopseq_candidates", "btgpu_hopseq_lookup",
            "btgpu_hopseq_fetch", "btgpu_pending", "btgpu_flush", "btgpu_device", "btgpu_device_count", "btgpu_last_timing", "btgpu_debug_fetch",
            "btgpu_debug_scan_symbols", "btgpu_debug_lut", "btgpu_process_host",
-           "btgpu_work_s16", "btgpu_process_host_s16", "btgpu_process_device_s16", "btgpu_exact_form"]
+           "btgpu_work_s16", "btgpu_process_host_s16", "btgpu_process_device_s16", "btgpu_exact_form", "btgpu_direct_form"]
 
 
 class BtgpuError(RuntimeError):
@@ -197,6 +199,8 @@ def lib():
     L.btgpu_last_timing.argtypes = [vp, ctypes.POINTER(Timing)]
     L.btgpu_exact_form.restype = ctypes.c_int
     L.btgpu_exact_form.argtypes = [vp]
+    L.btgpu_direct_form.restype = ctypes.c_int
+    L.btgpu_direct_form.argtypes = [vp]
     L.btgpu_debug_fetch.restype = ctypes.c_long
     L.btgpu_debug_fetch.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, vp]
     L.btgpu_debug_tables.restype = ctypes.c_int
@@ -467,6 +471,10 @@ class _MultiBlock:
     def exact_form(self):
         """EXACT_NONE, EXACT_SPARSE or EXACT_DENSE: the form of the exact rows' kernel this block runs."""
         return self._L.btgpu_exact_form(self._h)
+
+    def direct_form(self):
+        """DIRECT_VALU or DIRECT_MFMA: the kernel this block's direct-form banks run."""
+        return self._L.btgpu_direct_form(self._h)
 
     def debug_fetch(self, what, channel=0, first=0, count=0):
         dt = {0: np.complex64, 1: np.float32, 2: np.float64, 3: np.float64, 4: np.float64, 5: np.complex64,

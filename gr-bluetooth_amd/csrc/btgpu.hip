@@ -117,6 +117,11 @@ struct btgpu_handle {
     DevBuf d_tapsA;                  // the direct-form channel bank's taps as exact_rows_kernel's A operand (exact_pack_taps)
     bool ex_dense = false;           // exact rows run in the dense form (exact_dense.hip.h): ex_kern / ex_kern_s16 are its kernels
     DevBuf d_tapsD;                  // ... and its A operand (exact_pack_taps_dense); allocated on those handles only
+    // the direct-form banks on the matrix pipe (ddc_mfma.hip.h; BTGPU_FLAG_DIRECT_MFMA / BTGPU_DIRECT_FORM=mfma): the channel bank
+    // where the channelizer is DIRECT, the noise bank where the squelch is; their packed taps are allocated on those handles only
+    bool direct_mfma = false;
+    DevBuf d_tapsM_ch, d_tapsM_n;
+    int dm_qc_ch = 0, dm_qc_n = 0;   // tap blocks per chunk of the LDS ring (ddc_mfma_chunk)
     bool pipelined = false;          // front writes per-context buffers only: front(n+1) may overlap post(n)
     hipStream_t copy_stream = nullptr;
     hipStream_t spill_stream = nullptr;          // harvest: records beyond the eager copies (never behind an input copy)
@@ -223,7 +228,7 @@ struct btgpu_handle {
                          &d_Y, &d_Yn, &d_P, &d_Pt, &d_Q, &d_mmse, &d_atan, &d_aclo, &d_achi,
                          &d_le_hdr, &d_le_whiten, &d_le_index, &d_winbits,
                          &d_pfb_taps_ch, &d_pfb_tw, &d_binpos_ch, &d_binnat_ch, &d_rho_ch, &d_krot_ch, &d_b2map_fused, &d_b2map_fused_wide, &d_b2map_ch, &d_b2map_noise, &d_b2map_f320, &d_dftw_ch, &d_dftw_n, &d_arows_ch, &d_arows_n,
-                         &d_pfb_taps_n, &d_binpos_n, &d_krot_n, &d_h3, &d_w, &d_taps_s1, &d_rot_s1, &d_rotstep_s1, &d_prof, &d_pcol, &d_wh18, &d_tapsA, &d_tapsD};
+                         &d_pfb_taps_n, &d_binpos_n, &d_krot_n, &d_h3, &d_w, &d_taps_s1, &d_rot_s1, &d_rotstep_s1, &d_prof, &d_pcol, &d_wh18, &d_tapsA, &d_tapsD, &d_tapsM_ch, &d_tapsM_n};
         for (DevBuf *b : all) if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
         for (TailCtx &t : tc) {
             DevBuf *tb[] = {&t.d_winlen, &t.d_hits, &t.d_hitcount, &t.d_fin, &t.d_winfin, &t.d_symbits, &t.d_hdr, &t.d_d, &t.d_dcol,
@@ -329,6 +334,18 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
     int ntiles = 0, tiles_per_block = 1, tail_tiles = 0;
     const auto ddc = s16 ? ddc_direct_kernel_s16<2> : ddc_direct_kernel<2>;   // the direct-form bank for this call's input format
     bool fused_m = false;                                       // small-M banks: stage 1 ran inside the channel bank's kernel
+    // ... and its matrix-pipe form (ddc_mfma.hip.h): tiles of 128 outputs of one segment, row blocks in groups of kDmRB
+    auto launch_ddc_mfma = [&](const FilterBank &fb, const DevBuf &tp, int qc, long long first, const DevBuf &rot, const DevBuf &rotstep,
+                               float2 *Y, long long Gout, long long ys, int seg_len) {
+        DdcMfmaParams m{};
+        m.x = d_x; m.x_len = (long long)x_len; m.first = first;
+        m.D = d.decimation; m.NB = fb.ntp / d.decimation; m.QC = qc;
+        m.taps = (const float *)tp.p; m.rot = (const float2 *)rot.p; m.Q = fb.rot_period; m.rot_step_turns = (const double *)rotstep.p;
+        m.Y = Y; m.G = Gout; m.ystride = ys; m.nch = nch; m.seg_len = seg_len; m.seg_stride = seg_stride;
+        const unsigned gx = seg_len ? (unsigned)(((seg_len + kDmCols - 1) / kDmCols) * S) : (unsigned)((Gout + kDmCols - 1) / kDmCols);
+        const dim3 grid(gx, (unsigned)((exact_dense_blocks(nch) + kDmRB - 1) / kDmRB));
+        hipLaunchKernelGGL(s16 ? ddc_mfma_kernel_s16<0> : ddc_mfma_kernel, grid, dim3(kDmThreads), ddc_mfma_lds_bytes(m.D, qc), st, m);
+    };
 
     // ---- channel bank -> demodulated stream d[g][nch] + |Y|^2 tile sums (polyphase) or block sums P, Pt (direct) ----
     // the general-M bank (pfbg.hip.h): more than 48 KiB of dynamic LDS is asked for here, once per kernel launched, as below
@@ -387,12 +404,17 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
         HIPCHK(this, mark(1, st));
     } else {
         const LaunchShape &s = shape_ch;
+        if (direct_mfma)
+            launch_ddc_mfma(des.channel, d_tapsM_ch, dm_qc_ch, w0 + (long long)d.first_channel_sample, d_rot_ch, d_rotstep_ch,
+                            (float2 *)d_Y.p, G, ystride, seg_ch);
+        else {
         const unsigned gx = seg_ch ? (unsigned)(((seg_ch + s.T - 1) / s.T) * S) : (unsigned)((G + s.T - 1) / s.T);
         dim3 grid(gx, (unsigned)((nch + 1) / 2));
         hipLaunchKernelGGL(ddc, grid, dim3(s.T), s.lds, st, d_x, (long long)x_len,
                            w0 + (long long)d.first_channel_sample, d.decimation, des.channel.ntp, s.JC,
                            (const float2 *)d_taps_ch.p, (const float2 *)d_rot_ch.p, des.channel.rot_period,
                            (const double *)d_rotstep_ch.p, (float2 *)d_Y.p, G, ystride, nch, seg_ch, seg_stride);
+        }
         HIPCHK(this, mark(1, st));
         dim3 g2((unsigned)nb, (unsigned)nch);
         hipLaunchKernelGGL(energy_kernel, g2, dim3(256), 0, st, (const float2 *)d_Y.p, G,
@@ -436,12 +458,17 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
         HIPCHK(this, mark(4, st));
     } else {
         const LaunchShape &s = shape_n;
+        if (direct_mfma)
+            launch_ddc_mfma(des.noise, d_tapsM_n, dm_qc_n, w0 + (long long)d.first_noise_sample, d_rot_n, d_rotstep_n,
+                            (float2 *)d_Yn.p, Gn, ystride_n, seg_n);
+        else {
         const unsigned gx = seg_n ? (unsigned)(((seg_n + s.T - 1) / s.T) * S) : (unsigned)((Gn + s.T - 1) / s.T);
         dim3 grid(gx, (unsigned)((nch + 1) / 2));
         hipLaunchKernelGGL(ddc, grid, dim3(s.T), s.lds, st, d_x, (long long)x_len,
                            w0 + (long long)d.first_noise_sample, d.decimation, des.noise.ntp, s.JC,
                            (const float2 *)d_taps_n.p, (const float2 *)d_rot_n.p, des.noise.rot_period,
                            (const double *)d_rotstep_n.p, (float2 *)d_Yn.p, Gn, ystride_n, nch, seg_n, seg_stride);
+        }
         HIPCHK(this, mark(3, st));
         dim3 g2((unsigned)S, (unsigned)nch);
         hipLaunchKernelGGL(energy_kernel, g2, dim3(256), 0, st, (const float2 *)d_Yn.p, Gn,
@@ -1316,6 +1343,38 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         (void)hipFuncSetAttribute((const void *)h->ex_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(h->ex_lds, 64 * 1024));
         (void)hipFuncSetAttribute((const void *)h->ex_kern_s16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(h->ex_lds, 64 * 1024));
     }
+    // Which kernel runs the direct-form banks (ddc_mfma.hip.h): the matrix-pipe form on BTGPU_FLAG_DIRECT_MFMA and on
+    // BTGPU_DIRECT_FORM=mfma; BTGPU_DIRECT_FORM=valu asks for the vector-ALU form whatever the flag says (A/B timing).  The same bits
+    // either way.  VALU is the default: profiles/direct_mfma_ab.json, DESIGN.md section 4.1
+    if (!h->use_pfb || !h->use_staged) {
+        const char *df = getenv("BTGPU_DIRECT_FORM");
+        const bool flag = (cfg->flags & BTGPU_FLAG_DIRECT_MFMA) != 0;
+        bool want = flag || (df && std::strcmp(df, "mfma") == 0);
+        if (df && std::strcmp(df, "valu") == 0) want = false;
+        const int D = d.decimation;
+        h->dm_qc_ch = ddc_mfma_chunk(D, des.channel.ntp / D); h->dm_qc_n = ddc_mfma_chunk(D, des.noise.ntp / D);
+        if (want && (des.channel.ntp % D || des.noise.ntp % D || !h->dm_qc_ch || !h->dm_qc_n)) {
+            if (flag) return fail(BTGPU_EUNSUPPORTED);               // (a decimation beyond the LDS ring: the vector-ALU form serves it)
+            want = false;
+        }
+        h->direct_mfma = want;
+    }
+    if (h->direct_mfma) {
+        size_t lds = 64 * 1024;
+        if (!h->use_pfb) {
+            const std::vector<float> tp = pack_direct_mfma_taps(des.channel, d.decimation, kDmRB, kDmAhead);
+            TRY(h->upload(h->d_tapsM_ch, tp.data(), tp.size() * sizeof(float)));
+            lds = std::max(lds, ddc_mfma_lds_bytes(d.decimation, h->dm_qc_ch));
+        }
+        if (!h->use_staged) {
+            const std::vector<float> tp = pack_direct_mfma_taps(des.noise, d.decimation, kDmRB, kDmAhead);
+            TRY(h->upload(h->d_tapsM_n, tp.data(), tp.size() * sizeof(float)));
+            lds = std::max(lds, ddc_mfma_lds_bytes(d.decimation, h->dm_qc_n));
+        }
+        // more than 48 KiB of dynamic LDS is an opt-in per kernel
+        (void)hipFuncSetAttribute((const void *)ddc_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void *)ddc_mfma_kernel_s16<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    }
     for (int i = 0; i < h->nctx; i++) {
         auto &t = h->tc[i];
         if (h->use_pfb) {
@@ -1644,6 +1703,12 @@ int btgpu_exact_form(const btgpu_handle *h)
 {
     if (!h) return BTGPU_EINVAL;
     return !h->verify ? BTGPU_EXACT_NONE : (h->ex_dense ? BTGPU_EXACT_DENSE : BTGPU_EXACT_SPARSE);
+}
+
+int btgpu_direct_form(const btgpu_handle *h)
+{
+    if (!h) return BTGPU_EINVAL;
+    return h->direct_mfma ? BTGPU_DIRECT_MFMA : BTGPU_DIRECT_VALU;
 }
 
 int btgpu_last_timing(const btgpu_handle *h, btgpu_timing *out)

@@ -154,6 +154,14 @@ int make_fast_path(const Design &des, FastPath &fp);
 constexpr int kExactSlotRows = 1250;    // rows per slot that exact_rows_kernel's tiling is laid out for (kernels.hip.h kExSlotRows: eleven tiles per slot)
 bool exact_rows_available(const Design &des);
 
+// The A operand of ddc_mfma_kernel (ddc_mfma.hip.h) from a direct-form bank whose ntp is a whole number NB of blocks of D taps: one
+// linear stream per group of `rb` row blocks (16 channels each) in the order of use,
+//     [group][tap block q][16-byte group i of dpad(D) / 4][row block j of the group][lane of 64][step e of 4]
+// = the A operand of step r = 4 i + e of tap j = q D + r for lane l: row l & 31 = 2 (c % 16) + (re: 0, im: 1), k = l >> 5 --
+// (tr, -ti) for a re row, (ti, tr) for an im row (exact_pack_taps_dense's values, signs and swaps); zero in the pad steps and
+// past the last channel, and `ahead` * rb zero words of 1 KB behind the stream for its read-ahead.
+std::vector<float> pack_direct_mfma_taps(const FilterBank &b, int D, int rb, int ahead);
+
 // direct-form bank builder shared by the reference-filter banks and the staged squelch
 void build_direct_bank(FilterBank &b, const std::vector<float> &h, int low_ch, int nch, double extra_hz,
                        double center_freq, double fs, int decim);

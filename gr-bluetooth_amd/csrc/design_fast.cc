@@ -7,6 +7,7 @@
 //    the stage-1 rate whose coefficients are the least-squares fit that makes the COMPOSITE
 //    impulse response equal the reference filter (fit error ~1e-6 of the DC gain) -- and the
 //    per-slot mean |y|^2 is taken with band-limited quadrature weights on the stage-2 grid.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <numeric>
@@ -397,6 +398,30 @@ int make_fast_path(const Design &des, FastPath &fp)
     ns.available = true;
     (void)nch;
     return BTGPU_OK;
+}
+
+std::vector<float> pack_direct_mfma_taps(const FilterBank &b, int D, int rb, int ahead)
+{
+    const int DP = (D + 3) / 4 * 4, NI = DP / 4, NB = b.ntp / D, nblk = (b.nch + 15) / 16;
+    std::vector<float> out(((size_t)nblk * NB * NI + (size_t)ahead * rb) * 256, 0.f);
+    size_t w = 0;                                                // 1 KB word = one wave's 16-byte loads
+    for (int g0 = 0; g0 < nblk; g0 += rb) {
+        const int nbh = std::min(rb, nblk - g0);
+        for (int q = 0; q < NB; q++)
+            for (int i = 0; i < NI; i++)
+                for (int j = 0; j < nbh; j++, w++)
+                    for (int l = 0; l < 64; l++)
+                        for (int e = 0; e < 4; e++) {
+                            const int r = 4 * i + e, row = l & 31, kh = l >> 5, c = 16 * (g0 + j) + (row >> 1), im = row & 1;
+                            float tr = 0.f, ti = 0.f;
+                            if (r < D && c < b.nch) {
+                                tr = b.taps[((size_t)c * b.ntp + (size_t)q * D + r) * 2];
+                                ti = b.taps[((size_t)c * b.ntp + (size_t)q * D + r) * 2 + 1];
+                            }
+                            out[w * 256 + l * 4 + e] = im ? (kh ? tr : ti) : (kh ? -ti : tr);
+                        }
+    }
+    return out;
 }
 
 }  // namespace btgpu

@@ -12,6 +12,7 @@
 #include "pfbg.hip.h"
 #include "exact.hip.h"
 #include "exact_dense.hip.h"
+#include "ddc_mfma.hip.h"
 
 namespace btgpu {
 
@@ -58,6 +59,8 @@ BTGPU_S16_EX(50)
 #undef BTGPU_S16_EX
 // exact rows, dense form: one kernel for every decimation
 BTGPU_S16_KERNEL(exact_dense_kernel_s16<0>(ExactParams, const float2 *))
+// direct-form bank on the matrix pipe (BTGPU_FLAG_DIRECT_MFMA)
+BTGPU_S16_KERNEL(ddc_mfma_kernel_s16<0>(DdcMfmaParams))
 #undef BTGPU_S16_KERNEL
 
 }  // namespace btgpu

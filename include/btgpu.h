@@ -103,6 +103,11 @@ extern "C" {
                                            dense form is what runs at 52 .. 64 Msps, where the sparse one is not instantiated.  The environment's
                                            BTGPU_EXACT_FORM=dense | sparse does the same for A/B timing (profiles/exact_dense_ab.json) */
 
+#define BTGPU_FLAG_DIRECT_MFMA 0x1000    /* the direct-form banks (DIRECT channelizer, DIRECT squelch, the segmented rates: odd and fractional
+                                           samples per symbol) on the matrix pipe (csrc/ddc_mfma.hip.h) instead of the vector ALU.  The same
+                                           bits in every output either way; BTGPU_DIRECT_FORM=mfma | valu in the environment does the same
+                                           (profiles/direct_mfma_ab.json).  The staged squelch's direct stage 1 stays on the vector ALU */
+
 #define BTGPU_KIND_AC 0
 #define BTGPU_KIND_AA 1
 
@@ -279,6 +284,11 @@ int btgpu_last_timing(const btgpu_handle *h, btgpu_timing *out);
 #define BTGPU_EXACT_SPARSE 1   /* exact_rows_kernel<D>: one (channel, tile) pair at a time    */
 #define BTGPU_EXACT_DENSE  2   /* exact_dense_kernel: channels as the matrix rows             */
 int btgpu_exact_form(const btgpu_handle *h);
+
+/* Which kernel the handle's direct-form banks run (BTGPU_FLAG_DIRECT_MFMA); VALU also where it has none. */
+#define BTGPU_DIRECT_VALU 0    /* ddc_direct_kernel: one lane per output on the vector ALU    */
+#define BTGPU_DIRECT_MFMA 1    /* ddc_mfma_kernel: channels as the matrix rows                */
+int btgpu_direct_form(const btgpu_handle *h);
 
 /* ---- introspection for parity tests: copies an intermediate of the LAST batch ----
  * what: 0 channel-bank output Y (complex64 [channel][g]; DIRECT channelizer or BTGPU_FLAG_DEBUG_Y),
