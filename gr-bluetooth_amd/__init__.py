@@ -37,6 +37,7 @@ FLAG_EXACT_ALL = 1024     # no selection: every row of every channel exact (incl
 FLAG_EXACT_DENSE = 2048   # exact rows in the dense form also where the sparse one exists (include/btgpu.h)
 EXACT_NONE, EXACT_SPARSE, EXACT_DENSE = 0, 1, 2     # exact_form()
 FLAG_DIRECT_MFMA = 4096  # the direct-form banks on the matrix pipe (include/btgpu.h)
+FLAG_PAYLOAD_SWEEP = 8192  # (implies HEADERS) crc_check under the 64 CLK1-6 candidates on the GPU; poll_payloads (include/btgpu.h)
 DIRECT_VALU, DIRECT_MFMA = 0, 1                     # direct_form()
 KIND_AC, KIND_AA = 0, 1
 
@@ -89,7 +90,8 @@ EXPORTS = ["btgpu_design_query", "btgpu_acgen", "btgpu_filter_taps", "btgpu_stre
            "btgpu_hopseq_init_candidates", "btgpu_hopseq_winnow", "btgpu_hopseq_candidates", "btgpu_hopseq_lookup",
            "btgpu_hopseq_fetch", "btgpu_pending", "btgpu_flush", "btgpu_device", "btgpu_device_count", "btgpu_last_timing", "btgpu_debug_fetch",
            "btgpu_debug_scan_symbols", "btgpu_debug_lut", "btgpu_process_host",
-           "btgpu_work_s16", "btgpu_process_host_s16", "btgpu_process_device_s16", "btgpu_exact_form", "btgpu_direct_form"]
+           "btgpu_work_s16", "btgpu_process_host_s16", "btgpu_process_device_s16", "btgpu_exact_form", "btgpu_direct_form",
+           "btgpu_poll_payloads", "btgpu_debug_payload_sweep"]
 
 
 class BtgpuError(RuntimeError):
@@ -176,6 +178,12 @@ def lib():
     L.btgpu_poll_headers.restype = ctypes.c_int
     L.btgpu_poll_headers.argtypes = [vp, ctypes.POINTER(Hit), ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
                                      ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    L.btgpu_poll_payloads.restype = ctypes.c_int
+    L.btgpu_poll_payloads.argtypes = [vp, ctypes.POINTER(Hit), ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    L.btgpu_debug_payload_sweep.restype = ctypes.c_long
+    L.btgpu_debug_payload_sweep.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p]
     L.btgpu_hopseq_create.restype = ctypes.c_int
     L.btgpu_hopseq_create.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     L.btgpu_hopseq_destroy.restype = None
@@ -283,6 +291,27 @@ def scan_symbols(symbols, policy=1, device=-1, cap=1 << 16):
     if n > cap:
         raise BtgpuError(EOVERFLOW, "%d records, cap %d" % (n, cap))
     return [(out[i].offset, out[i].lap, out[i].ac_errors) for i in range(n)]
+
+
+HEADER_DTYPE = np.dtype([("uap", np.uint8, 64), ("type", np.uint8, 64), ("fec13_ok", "<i4"), ("reserved", "<i4")])
+CRC_SWEEP_DTYPE = np.dtype([("verdict", "<i2", 64), ("length", "<i4"), ("reserved", "<i4")])
+
+
+def debug_payload_sweep(packets, to_header=72, device=-1):
+    """header_sweep_kernel + payload_sweep_kernel straight on captured packets (btgpu_debug_payload_sweep): `packets` is a
+    list of symbol arrays (0/1 per symbol) that start at the access-code offset -- the preamble with to_header = 72, the sync
+    word with 68.  Returns (headers [n] of HEADER_DTYPE, sweeps [n] of CRC_SWEEP_DTYPE)."""
+    n = len(packets)
+    lens = np.array([len(p) for p in packets], np.int32)
+    stride = max(int(lens.max()) if n else 0, 1)
+    buf = np.zeros((n, stride), np.uint8)
+    for i, p in enumerate(packets):
+        buf[i, :lens[i]] = np.asarray(p, np.uint8) & 1
+    hdrs, crcs = np.zeros(n, HEADER_DTYPE), np.zeros(n, CRC_SWEEP_DTYPE)
+    got = lib().btgpu_debug_payload_sweep(buf.ctypes.data, lens.ctypes.data, n, stride, device, to_header, hdrs.ctypes.data, crcs.ctypes.data)
+    if got < 0:
+        raise BtgpuError(int(got), "btgpu_debug_payload_sweep")
+    return hdrs, crcs
 
 
 def staged_design(sample_rate, center_freq):
@@ -444,7 +473,7 @@ class _MultiBlock:
             hits, syms, lens = hits[:got], syms[:got], lens[:got]
         return hits, syms, lens
 
-    HEADER_DTYPE = np.dtype([("uap", np.uint8, 64), ("type", np.uint8, 64), ("fec13_ok", "<i4"), ("reserved", "<i4")])
+    HEADER_DTYPE = HEADER_DTYPE
 
     def poll_headers(self, sym_cap=3125, max_hits=1 << 16):
         """poll_symbols plus, per hit, what classic_packet::try_clock gives for the 64 CLK1-6
@@ -462,6 +491,25 @@ class _MultiBlock:
                 raise BtgpuError(got, "btgpu_poll_headers")
             hits, hdrs, syms, lens = hits[:got], hdrs[:got], syms[:got], lens[:got]
         return hits, hdrs, syms, lens
+
+    CRC_SWEEP_DTYPE = CRC_SWEEP_DTYPE
+
+    def poll_payloads(self, sym_cap=3125, max_hits=1 << 16):
+        """poll_headers plus, per hit, what classic_packet::crc_check gives for the 64 CLK1-6 candidates (needs
+        flags=FLAG_PAYLOAD_SWEEP): (hits, headers, sweeps [n] of CRC_SWEEP_DTYPE, symbols, lens)."""
+        n = min(max(self._L.btgpu_pending(self._h), 0), max_hits)
+        hits = np.zeros(max(n, 1), self.HIT_DTYPE)
+        hdrs = np.zeros(max(n, 1), self.HEADER_DTYPE)
+        crcs = np.zeros(max(n, 1), self.CRC_SWEEP_DTYPE)
+        syms = np.zeros((max(n, 1), sym_cap), np.uint8)
+        lens = np.zeros(max(n, 1), np.int32)
+        # (asked even where nothing is pending: a handle without the flag answers BTGPU_EUNSUPPORTED)
+        got = self._L.btgpu_poll_payloads(self._h, hits.ctypes.data_as(ctypes.POINTER(Hit)), hdrs.ctypes.data, crcs.ctypes.data,
+                                          syms.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), sym_cap,
+                                          lens.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n)
+        if got < 0:
+            raise BtgpuError(got, "btgpu_poll_payloads")
+        return hits[:got], hdrs[:got], crcs[:got], syms[:got], lens[:got]
 
     def timing(self):
         t = Timing()

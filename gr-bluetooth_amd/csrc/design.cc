@@ -240,6 +240,7 @@ int make_design(const btgpu_config &cfg, Design &o)
     if (corr == BTGPU_CORRELATOR_AUTO) corr = cfg.mode == BTGPU_MODE_LAP ? BTGPU_CORRELATOR_BTBB : BTGPU_CORRELATOR_INTREE;
     if (corr != BTGPU_CORRELATOR_INTREE && corr != BTGPU_CORRELATOR_BTBB) return BTGPU_EINVAL;
     if (corr == BTGPU_CORRELATOR_BTBB && cfg.mode != BTGPU_MODE_LAP) return BTGPU_EUNSUPPORTED;   // multi_sniffer uses sniff_ac
+    if ((cfg.flags & BTGPU_FLAG_PAYLOAD_SWEEP) && cfg.mode != BTGPU_MODE_SNIFFER) return BTGPU_EUNSUPPORTED;   // multi_LAP decodes no packets
     o.cfg = cfg;
     btgpu_design &d = o.d;
     std::memset(&d, 0, sizeof d);

@@ -5,6 +5,7 @@
 // the number of items consumed -- a whole number of slots (the reference always returns
 // exactly one slot; this block consumes every whole slot it was handed).
 #include <cstdio>
+#include <cstdlib>
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
@@ -30,8 +31,12 @@ multi_block::multi_block(double sample_rate, double center_freq, double squelch_
     // multi_hopper (lib/multi_hopper_impl.cc:52-56) has the sniffer's symbol history but no LE pass
     // multi_LAP prints the LAP of a hit and nothing that depends on the rest of the window
     // (lib/multi_LAP_impl.cc:93-110): no clock-recovery continuation for hit.nsym
-    const int flags = mode == BTGPU_MODE_SNIFFER ? ((hopper ? 0 : BTGPU_FLAG_LE) | BTGPU_FLAG_HEADERS | BTGPU_FLAG_EXACT_PAYLOAD) : BTGPU_FLAG_NO_NSYM;
+    int flags = mode == BTGPU_MODE_SNIFFER ? ((hopper ? 0 : BTGPU_FLAG_LE) | BTGPU_FLAG_HEADERS | BTGPU_FLAG_EXACT_PAYLOAD) : BTGPU_FLAG_NO_NSYM;
     d_headers = (flags & BTGPU_FLAG_HEADERS) != 0;
+    // crc_check under the 64 clock candidates on the GPU too (csrc/payload_sweep.hip.h): off unless the environment asks
+    const char *ps = getenv("BTGPU_PAYLOAD_SWEEP");
+    d_payloads = d_headers && ps && atoi(ps) == 1;
+    if (d_payloads) flags |= BTGPU_FLAG_PAYLOAD_SWEEP;
     d_sample_rate = sample_rate;
     d_center_freq = center_freq;
     d_target_snr = squelch_threshold;
@@ -93,14 +98,23 @@ void multi_block::drain(btgpu_handle *g)
 {
     std::vector<btgpu_hit> buf(256);
     if (d_headers) {
-        const int cap = 3125;                         // classic_packet keeps at most MAX_SYMBOLS
+        // classic_packet keeps at most MAX_SYMBOLS = 3125; with the payload sweep a packet is handed every symbol the sweep saw
+        // (up to 3840: btgpu_crc_sweep.length must equal the count handed over for its verdicts to be used), a classic packet
+        // clips them itself and the LE handler gets what it always got
+        const int cap = d_payloads ? 3840 : 3125;
         std::vector<uint8_t> syms((size_t)buf.size() * cap);
         std::vector<int> lens(buf.size());
         std::vector<btgpu_header> hdrs(buf.size());
+        std::vector<btgpu_crc_sweep> crcs(d_payloads ? buf.size() : 0);
         for (;;) {
-            int n = btgpu_poll_headers(g, buf.data(), hdrs.data(), syms.data(), cap, lens.data(), (int)buf.size());
+            int n = d_payloads ? btgpu_poll_payloads(g, buf.data(), hdrs.data(), crcs.data(), syms.data(), cap, lens.data(), (int)buf.size())
+                               : btgpu_poll_headers(g, buf.data(), hdrs.data(), syms.data(), cap, lens.data(), (int)buf.size());
             if (n <= 0) break;
-            for (int i = 0; i < n; i++) handle_hit(buf[i], &hdrs[i], syms.data() + (size_t)i * cap, lens[i]);
+            for (int i = 0; i < n; i++) {
+                d_crc_now = d_payloads && buf[i].kind == BTGPU_KIND_AC ? &crcs[i] : nullptr;
+                handle_hit(buf[i], &hdrs[i], syms.data() + (size_t)i * cap, buf[i].kind == BTGPU_KIND_AC ? lens[i] : std::min(lens[i], 3125));
+            }
+            d_crc_now = nullptr;
         }
     } else {
         for (;;) {
@@ -237,7 +251,7 @@ protected:
         }
         // ac() and everything it calls (lib/multi_sniffer_impl.cc:169-365): the "time ..." prefix,
         // then ID, the UAP/CLK1-6 discovery dialogue or the decoded packet
-        const std::string text = d_handlers.ac(h, *hdr, syms, nsyms);
+        const std::string text = d_handlers.ac(h, *hdr, syms, nsyms, d_crc_now);
         fputs(text.c_str(), stdout);
     }
 };
@@ -266,7 +280,7 @@ protected:
     host::tap_sink d_tap;
     void handle_hit(const btgpu_hit &h, const btgpu_header *hdr, const uint8_t *syms, int nsyms) override
     {
-        const std::string text = d_handlers.hit(h, *hdr, syms, nsyms);
+        const std::string text = d_handlers.hit(h, *hdr, syms, nsyms, d_crc_now);
         if (!text.empty()) fputs(text.c_str(), stdout);
     }
 };

@@ -141,9 +141,12 @@ uint32_t classic_packet::bits(const uint8_t *air, int n)
     return v;
 }
 
-classic_packet::classic_packet(const uint8_t *symbols, int length, uint32_t clkn, int channel, const btgpu_header &sweep)
+classic_packet::classic_packet(const uint8_t *symbols, int length, uint32_t clkn, int channel, const btgpu_header &sweep,
+                               const btgpu_crc_sweep *crc)
     : d_symbols(MAX_SYMBOLS + 64, 0), d_clkn(clkn), d_channel(channel), d_sweep(sweep), d_payload(3000, 0)
 {
+    // the length guards of crc_check depend on the symbol count: the GPU's verdicts hold for the count it saw, no other
+    if (crc && sweep.fec13_ok && crc->length == length) { d_crc = *crc; d_have_crc = true; }
     if (length > MAX_SYMBOLS) length = MAX_SYMBOLS;
     if (length < 0) length = 0;
     if (length > 0) std::memcpy(d_symbols.data(), symbols, (size_t)length);   // (a hit may hand over no symbols at all)
@@ -396,6 +399,9 @@ int classic_packet::HV(int clock)
 
 int classic_packet::crc_check(int clock)
 {
+    // the GPU's verdict is for what try_clock(clock) left in d_type / d_UAP
+    if (d_have_crc && d_crc.verdict[clock & 63] >= 0 && d_type == d_sweep.type[clock & 63] && d_uap == d_sweep.uap[clock & 63])
+        return d_crc.verdict[clock & 63];
     int r = 1;                                     // 1 inconclusive, > 1 positive, 0 negative
     switch (d_type) {
         case 2: r = fhs(clock); break;
@@ -686,7 +692,8 @@ bool basic_rate_piconet::uap_from_header(classic_packet &pkt, std::string &out)
 }
 
 // ------------------------------------------------------------------ hopper_handlers
-std::string hopper_handlers::hit(const btgpu_hit &hit, const btgpu_header &sweep, const uint8_t *symbols, int nsymbols)
+std::string hopper_handlers::hit(const btgpu_hit &hit, const btgpu_header &sweep, const uint8_t *symbols, int nsymbols,
+                                 const btgpu_crc_sweep *crc)
 {
     std::string out;
     if (hit.slot != d_slot) {                      // a new work() call of the reference
@@ -728,7 +735,7 @@ std::string hopper_handlers::hit(const btgpu_hit &hit, const btgpu_header &sweep
         }
         return out;
     }
-    classic_packet pkt(symbols, nsymbols, clkn, hit.channel, sweep);
+    classic_packet pkt(symbols, nsymbols, clkn, hit.channel, sweep, crc);
     if (pkt.lap() != d_lap || !pkt.header_present()) return out;
     d_slot_done = true;                            // the reference breaks out of its channel loop here
     if (!d_piconet.have_clk6()) {
@@ -745,11 +752,12 @@ std::string hopper_handlers::hit(const btgpu_hit &hit, const btgpu_header &sweep
 }
 
 // ----------------------------------------------------------------- sniffer_handlers
-std::string sniffer_handlers::ac(const btgpu_hit &hit, const btgpu_header &sweep, const uint8_t *symbols, int nsymbols)
+std::string sniffer_handlers::ac(const btgpu_hit &hit, const btgpu_header &sweep, const uint8_t *symbols, int nsymbols,
+                                 const btgpu_crc_sweep *crc)
 {
     std::string out;
     const uint32_t clkn = (uint32_t)(hit.slot & 0x7ffffff);
-    auto pkt = std::make_shared<classic_packet>(symbols, nsymbols, clkn, hit.channel, sweep);
+    auto pkt = std::make_shared<classic_packet>(symbols, nsymbols, clkn, hit.channel, sweep, crc);
     const uint32_t lap = pkt->lap();
     appendf(out, "time %6d, snr=%.1f, channel %2d, LAP %06x ", (int)clkn, hit.snr_db, hit.channel, lap);
     if (!pkt->header_present()) { id(lap, out); return out; }
@@ -846,6 +854,13 @@ extern "C" int bt_host_crc_check(const uint8_t *symbols, int length, int clock, 
     std::memset(&none, 0, sizeof none);
     gr::bluetooth::host::classic_packet pkt(symbols, length, 0, 0, none);
     pkt.force_header(type, (uint8_t)uap);
+    return pkt.crc_check(clock);
+}
+
+extern "C" int bt_host_crc_check_swept(const uint8_t *symbols, int length, int clock, const btgpu_header *sweep, const btgpu_crc_sweep *crc)
+{
+    gr::bluetooth::host::classic_packet pkt(symbols, length, 0, 0, *sweep, crc);
+    (void)pkt.try_clock(clock);
     return pkt.crc_check(clock);
 }
 

@@ -47,8 +47,10 @@ class classic_packet
 {
 public:
     static constexpr int MAX_SYMBOLS = 3125;
-    // symbols from the access code on, one per byte; `sweep` = the GPU's try_clock results
-    classic_packet(const uint8_t *symbols, int length, uint32_t clkn, int channel, const btgpu_header &sweep);
+    // symbols from the access code on, one per byte; `sweep` = the GPU's try_clock results; `crc` (may be null) = its
+    // crc_check results for the same 64 clocks (btgpu_poll_payloads)
+    classic_packet(const uint8_t *symbols, int length, uint32_t clkn, int channel, const btgpu_header &sweep,
+                   const btgpu_crc_sweep *crc = nullptr);
 
     uint32_t lap() const { return d_lap; }
     uint32_t clkn() const { return d_clkn; }
@@ -58,7 +60,7 @@ public:
     bool header_present() const;                       // lib/packet_impl.cc:1205-1242
 
     uint8_t try_clock(int clock);                      // :1046-1063, served from the sweep
-    int crc_check(int clock);                          // :612-671
+    int crc_check(int clock);                          // :612-671, served from the payload sweep where that was computed on this packet
     void set_clock(uint32_t clock, bool have27);       // :582-594
     void set_uap(uint8_t uap) { d_uap = uap; }
     void decode(std::string &out);                     // :169-175, :1066-1165
@@ -99,6 +101,8 @@ private:
     int d_channel;
     uint32_t d_lap;
     btgpu_header d_sweep;
+    btgpu_crc_sweep d_crc;                             // verdicts of the GPU's payload sweep ...
+    bool d_have_crc = false;                           // ... usable: computed on exactly the symbols handed over
     int d_type = 0;
     uint8_t d_uap = 0;
     uint32_t d_clock = 0;
@@ -168,7 +172,8 @@ public:
     hopper_handlers(uint32_t lap, bool aliased, int low_channel, int high_channel)
         : d_lap(lap & 0xffffff), d_aliased(aliased), d_low(low_channel), d_high(high_channel), d_piconet(lap & 0xffffff) {}
     // records in (slot, channel, offset) order; returns the text the reference prints
-    std::string hit(const btgpu_hit &hit, const btgpu_header &sweep, const uint8_t *symbols, int nsymbols);
+    std::string hit(const btgpu_hit &hit, const btgpu_header &sweep, const uint8_t *symbols, int nsymbols,
+                    const btgpu_crc_sweep *crc = nullptr);
     const basic_rate_piconet &piconet() const { return d_piconet; }
     void set_tap(tap_sink *t) { d_tap = t; }
 
@@ -187,7 +192,8 @@ class sniffer_handlers
 {
 public:
     // one classic hit, in the order work() reports them; returns the text the reference prints
-    std::string ac(const btgpu_hit &hit, const btgpu_header &sweep, const uint8_t *symbols, int nsymbols);
+    std::string ac(const btgpu_hit &hit, const btgpu_header &sweep, const uint8_t *symbols, int nsymbols,
+                   const btgpu_crc_sweep *crc = nullptr);
     void set_tap(tap_sink *t) { d_tap = t; }
 
 private:
@@ -207,6 +213,8 @@ private:
 // C entry points onto the packet parsers, for differential tests against the oracle
 extern "C" {
 int bt_host_crc_check(const uint8_t *symbols, int length, int clock, int type, int uap);
+// try_clock(clock) + crc_check(clock) of a packet that was given both sweeps
+int bt_host_crc_check_swept(const uint8_t *symbols, int length, int clock, const btgpu_header *sweep, const btgpu_crc_sweep *crc);
 int bt_host_decode_print(const uint8_t *symbols, int length, int uap, uint32_t clock, int have27, char *out, int cap);
 }
 #endif

@@ -29,6 +29,8 @@ protected:
     double d_sample_rate = 0, d_center_freq = 0, d_target_snr = 0;
     int d_mode = 0;
     bool d_headers = false;               // records come with symbols and the header sweep
+    bool d_payloads = false;              // ... and the payload sweep (BTGPU_PAYLOAD_SWEEP=1 in the environment)
+    const btgpu_crc_sweep *d_crc_now = nullptr;   // the payload sweep of the record handle_hit is looking at (or null)
     bool d_warned_turned_away = false;    // the "second run's list was full" warning has been printed
 
     // forwards one scheduler call to btgpu_work(); returns the number of items consumed

@@ -108,6 +108,12 @@ extern "C" {
                                            bits in every output either way; BTGPU_DIRECT_FORM=mfma | valu in the environment does the same
                                            (profiles/direct_mfma_ab.json).  The staged squelch's direct stage 1 stays on the vector ALU */
 
+#define BTGPU_FLAG_PAYLOAD_SWEEP 0x2000   /* (implies HEADERS) behind the header sweep, classic_packet::crc_check under the same 64 CLK1-6 candidates
+                                           on the GPU (csrc/payload_sweep.hip.h): FEC 2/3, unwhitening, payload header, CRC-16 -- the other
+                                           half of what basic_rate_piconet::UAP_from_header asks of a packet; btgpu_poll_payloads.  Sniffer
+                                           mode only (multi_LAP has no packet handlers: BTGPU_EUNSUPPORTED from btgpu_design_query and
+                                           btgpu_create).  Without the flag nothing of it is allocated or launched */
+
 #define BTGPU_KIND_AC 0
 #define BTGPU_KIND_AA 1
 
@@ -273,6 +279,20 @@ typedef struct btgpu_header {
 /* btgpu_poll_symbols plus the header sweep of each record (zeroed for kind AA); needs BTGPU_FLAG_HEADERS */
 int btgpu_poll_headers(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr, uint8_t *symbols, int sym_cap,
                        int *sym_len, int max_hits);
+/* What classic_packet::crc_check(clock) returns right after try_clock(clock) on a fresh packet, for clock = 0..63
+ * (lib/packet_impl.cc:612-671): 0 refuted (FHS, DM1 and HV1 only), 1 inconclusive, 10 CRC correct, 1000 FHS CRC correct; -1 = not
+ * computed (fec13_ok = 0 -- try_clock fails, crc_check is never asked -- and kind AA).  Type and UAP are the header sweep's for the
+ * same clock.  `length` is the number of symbols from hit.offset on that the verdicts were computed on: min(nsym, 3840 - offset), the
+ * packed symbols the device keeps per hit window (symbols beyond it read as 0).  The length guards of crc_check depend on it: a
+ * host layer that hands its packet another number of symbols must compute its own verdicts (host/classic.cc does). */
+typedef struct btgpu_crc_sweep {
+    int16_t verdict[64];
+    int32_t length;
+    int32_t reserved;
+} btgpu_crc_sweep;
+/* btgpu_poll_headers plus the payload sweep of each record; needs BTGPU_FLAG_PAYLOAD_SWEEP (BTGPU_EUNSUPPORTED without) */
+int btgpu_poll_payloads(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr, btgpu_crc_sweep *crc, uint8_t *symbols, int sym_cap,
+                        int *sym_len, int max_hits);
 int btgpu_pending(const btgpu_handle *h);
 /* Wait for every enqueued batch and move its records to the poll queue (BTGPU_FLAG_ASYNC). */
 int btgpu_flush(btgpu_handle *h);
@@ -314,6 +334,14 @@ int btgpu_debug_lut(const char *name, void *out, int cap_bytes);
  * symbol offset, lap, ac_errors, nsym = n - offset; ordered by offset.  Returns the number of
  * records (the first `cap` are written) or a negative error.  No handle needed. */
 long btgpu_debug_scan_symbols(const uint8_t *symbols, size_t n, int device, int policy, btgpu_hit *out, long cap);
+
+/* ---- parity entry: the two sweeps on captured packets ----
+ * `n_packets` symbol arrays, one symbol per byte (0/1), packet i at symbols[i * stride] with lengths[i] (<= stride, <= 3840)
+ * symbols from the access-code offset on: the preamble with to_header = 72 (the in-tree correlator's offset), the sync word with
+ * to_header = 68 (libbtbb's).  Packs them, runs header_sweep_kernel and payload_sweep_kernel on them as the tail of a batch does
+ * (offset 0, nsym = lengths[i]) and returns both records per packet.  Returns n_packets or a negative error.  No handle needed. */
+long btgpu_debug_payload_sweep(const uint8_t *symbols, const int32_t *lengths, int n_packets, int stride, int device, int to_header,
+                               btgpu_header *hdr, btgpu_crc_sweep *crc);
 
 /* ---- hop reversal: the piconet's complete hopping sequence on the GPU ----
  * Replaces basic_rate_piconet_impl::init_hop_reversal's precalc + address_precalc + gen_hops
