@@ -90,7 +90,8 @@ EXPORTS = ["btgpu_design_query", "btgpu_acgen", "btgpu_filter_taps", "btgpu_stre
            "btgpu_hopseq_init_candidates", "btgpu_hopseq_winnow", "btgpu_hopseq_candidates", "btgpu_hopseq_lookup",
            "btgpu_hopseq_fetch", "btgpu_pending", "btgpu_flush", "btgpu_device", "btgpu_device_count", "btgpu_last_timing", "btgpu_debug_fetch",
            "btgpu_debug_scan_symbols", "btgpu_debug_lut", "btgpu_process_host",
-           "btgpu_work_s16", "btgpu_process_host_s16", "btgpu_process_device_s16", "btgpu_exact_form", "btgpu_direct_form",
+           "btgpu_work_s16", "btgpu_process_host_s16", "btgpu_process_device_s16",
+           "btgpu_work_s8", "btgpu_process_host_s8", "btgpu_process_device_s8", "btgpu_exact_form", "btgpu_direct_form",
            "btgpu_poll_payloads", "btgpu_debug_payload_sweep"]
 
 
@@ -171,6 +172,13 @@ def lib():
     L.btgpu_process_device_s16.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, vp]
     L.btgpu_process_host_s16.restype = ctypes.c_int
     L.btgpu_process_host_s16.argtypes = [vp, ctypes.POINTER(ctypes.c_int16), ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64]
+    # complex int8 input: the same again, 2 bytes per complex sample
+    L.btgpu_work_s8.restype = ctypes.c_int
+    L.btgpu_work_s8.argtypes = [vp, ctypes.POINTER(ctypes.c_int8), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    L.btgpu_process_device_s8.restype = ctypes.c_int
+    L.btgpu_process_device_s8.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, vp]
+    L.btgpu_process_host_s8.restype = ctypes.c_int
+    L.btgpu_process_host_s8.argtypes = [vp, ctypes.POINTER(ctypes.c_int8), ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64]
     L.btgpu_poll.restype = ctypes.c_int
     L.btgpu_poll.argtypes = [vp, ctypes.POINTER(Hit), ctypes.c_int]
     L.btgpu_pending.restype = ctypes.c_int
@@ -337,16 +345,20 @@ def _as_f32(iq):
     return a
 
 
-FORMAT_F32, FORMAT_S16 = "f32", "s16"      # input formats of work / process_host / process_device
+FORMAT_F32, FORMAT_S16, FORMAT_S8 = "f32", "s16", "s8"      # input formats of work / process_host / process_device
+_CTYPE = {FORMAT_F32: ctypes.c_float, FORMAT_S16: ctypes.c_int16, FORMAT_S8: ctypes.c_int8}
+_SUFFIX = {FORMAT_F32: "", FORMAT_S16: "_s16", FORMAT_S8: "_s8"}
 
 
 def _as_input(iq):
-    """(flat array, is_int16) of an IQ argument: complex64 / interleaved float32, or interleaved int16 ([n, 2] or flat),
-    which goes to the *_s16 entries as it is -- widened on the GPU, never scaled."""
+    """(flat array, format) of an IQ argument: complex64 / interleaved float32, or interleaved int16 / int8 ([n, 2] or flat),
+    which goes to the *_s16 / *_s8 entries as it is -- widened on the GPU, never scaled."""
     a = np.ascontiguousarray(iq)
     if a.dtype == np.int16:
-        return a.reshape(-1), True
-    return _as_f32(a).reshape(-1), False
+        return a.reshape(-1), FORMAT_S16
+    if a.dtype == np.int8:
+        return a.reshape(-1), FORMAT_S8
+    return _as_f32(a).reshape(-1), FORMAT_F32
 
 
 class _MultiBlock:
@@ -393,15 +405,11 @@ class _MultiBlock:
     def work(self, input_items):
         """work(): input_items = history()-1 old samples followed by the new ones.
         Returns the number of items consumed (a whole number of slots)."""
-        a, s16 = _as_input(input_items)
+        a, fmt = _as_input(input_items)
         consumed = ctypes.c_size_t()
-        if s16:
-            rc = self._L.btgpu_work_s16(self._h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), len(a) // 2,
-                                        ctypes.byref(consumed))
-        else:
-            rc = self._L.btgpu_work(self._h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), len(a) // 2,
-                                    ctypes.byref(consumed))
-        self._check(rc, "btgpu_work_s16" if s16 else "btgpu_work")
+        f = getattr(self._L, "btgpu_work" + _SUFFIX[fmt])
+        rc = f(self._h, a.ctypes.data_as(ctypes.POINTER(_CTYPE[fmt])), len(a) // 2, ctypes.byref(consumed))
+        self._check(rc, "btgpu_work" + _SUFFIX[fmt])
         return consumed.value
 
     def push(self, iq):
@@ -411,22 +419,21 @@ class _MultiBlock:
 
     def process_device(self, dev_ptr, n_complex, first_slot, n_slots, left_margin=0, stream=None, fmt=FORMAT_F32):
         """dev_ptr[left_margin] = absolute sample first_slot*slot-(history()-1).  fmt=FORMAT_S16: the segment is interleaved
-        int16 (4 bytes per complex sample, dev_ptr 8-byte aligned)."""
-        f = self._L.btgpu_process_device_s16 if fmt == FORMAT_S16 else self._L.btgpu_process_device
+        int16 (4 bytes per complex sample, dev_ptr 8-byte aligned); fmt=FORMAT_S8: interleaved int8 (2 bytes, 4-byte aligned)."""
+        f = getattr(self._L, "btgpu_process_device" + _SUFFIX[fmt])
         rc = f(self._h, ctypes.c_void_p(dev_ptr), n_complex, left_margin, first_slot, n_slots, ctypes.c_void_p(stream or 0))
         self._check(rc, "btgpu_process_device")
 
     def process_host(self, iq, first_slot, n_slots, left_margin=0, fmt=FORMAT_F32):
-        """btgpu_process_host: the segment lies in HOST memory (a numpy array -- complex64, float32 or int16 --, or the address
-        of page-locked memory as an int together with its length in complex samples: (ptr, n_complex), int16 with
-        fmt=FORMAT_S16); iq[left_margin] = absolute sample first_slot*slot-(history()-1)."""
+        """btgpu_process_host: the segment lies in HOST memory (a numpy array -- complex64, float32, int16 or int8 --, or the
+        address of page-locked memory as an int together with its length in complex samples: (ptr, n_complex), int16 / int8 with
+        fmt=FORMAT_S16 / FORMAT_S8); iq[left_margin] = absolute sample first_slot*slot-(history()-1)."""
         if isinstance(iq, tuple):
-            s16 = fmt == FORMAT_S16
-            ptr, n = ctypes.cast(ctypes.c_void_p(int(iq[0])), ctypes.POINTER(ctypes.c_int16 if s16 else ctypes.c_float)), int(iq[1])
+            ptr, n = ctypes.cast(ctypes.c_void_p(int(iq[0])), ctypes.POINTER(_CTYPE[fmt])), int(iq[1])
         else:
-            a, s16 = _as_input(iq)
-            ptr, n = a.ctypes.data_as(ctypes.POINTER(ctypes.c_int16 if s16 else ctypes.c_float)), len(a) // 2
-        f = self._L.btgpu_process_host_s16 if s16 else self._L.btgpu_process_host
+            a, fmt = _as_input(iq)
+            ptr, n = a.ctypes.data_as(ctypes.POINTER(_CTYPE[fmt])), len(a) // 2
+        f = getattr(self._L, "btgpu_process_host" + _SUFFIX[fmt])
         rc = f(self._h, ptr, n, left_margin, first_slot, n_slots)
         self._check(rc, "btgpu_process_host")
 

@@ -55,12 +55,10 @@ inline bool pick_shape(int D, int ntp, LaunchShape &s)
 }
 
 
-// K<ARGS...> or its int16-input twin K_s16<ARGS...> (kernels.hip.h "Input formats").  The launch helpers below take the format
-// as a trailing argument, float by default.
-#define BTGPU_KIN(s16, K, ...) ((s16) ? K##_s16<__VA_ARGS__> : K<__VA_ARGS__>)
+// The launch helpers below take the input format (kernels.hip.h "Input formats", BTGPU_KIN) as a trailing argument, float by default.
 
 struct BankBuffers {                        // device (or emulated) memory
-    const float2 *x = nullptr;              // the input stream; int16 samples behind the same pointer type when s16 is passed
+    const float2 *x = nullptr;              // the input stream; int16 / int8 samples behind the same pointer type when fmt says so
     const float2 *taps_ch = nullptr, *twiddle = nullptr, *krot_ch = nullptr, *rho_ch = nullptr;
     const int *binpos_ch = nullptr, *binnat_ch = nullptr;
     const uint16_t *b2map_fused = nullptr, *b2map_fused_wide = nullptr, *b2map_ch = nullptr, *b2map_noise = nullptr, *b2map_f320 = nullptr;
@@ -88,10 +86,10 @@ inline size_t bank_lds_bytes(int span_samples, int nt, int nrows, bool chan, boo
 template <class Launcher>
 inline int launch_channel_bank(const Design &des, const FastPath &fp, bool fuse_noise, const BankBuffers &b,
                                size_t x_len, long long w0, int S, long long G, int nb, Launcher &&L, int variant = kBankLegacy,
-                               bool s16 = false)
+                               int fmt = 0)
 {
-    // (int16 input: the default kernel and the round-2 kernel it falls back to; the A/B variants exist for float input only)
-    if (s16) variant = variant >= kBankRun256 ? (int)kBankRun256 : (int)kBankLegacy;
+    // (int16 / int8 input: the default kernel and the round-2 kernel it falls back to; the A/B variants exist for float input only)
+    if (fmt != kInF32) variant = variant >= kBankRun256 ? (int)kBankRun256 : (int)kBankLegacy;
     const bool wide = variant == kBankLegacyWide;
     const btgpu_design &d = des.d;
     const PfbBank &bk = fp.channel;
@@ -156,22 +154,22 @@ inline int launch_channel_bank(const Design &des, const FastPath &fp, bool fuse_
                 static const int runs_env = [] { const char *e = getenv("BTGPU_BANK_RUNS"); return e ? atoi(e) : 0; }();
                 const int nr10 = runs_env > 0 ? (runs_env < grid ? runs_env : grid) : (grid + 2 * kBankKT - 1) / (2 * kBankKT);
                 // + the lean epilogue where the per-step rotation of every channel is +-1 (100 Msps: always)
-                if (bk.real_taps && p.rho_real) L(BTGPU_KIN(s16, pfb100f_kernel, kBankThreads, true, 2 * kBankKT, 255), nr10, kBankThreads, lds, p);
-                else if (bk.real_taps) L(BTGPU_KIN(s16, pfb100f_kernel, kBankThreads, true, 2 * kBankKT, 7 + 224), nr10, kBankThreads, lds, p);
-                else L(BTGPU_KIN(s16, pfb100f_kernel, kBankThreads, false, 2 * kBankKT, 3 + 224), nr10, kBankThreads, lds, p);
+                if (bk.real_taps && p.rho_real) L(BTGPU_KIN(fmt,pfb100f_kernel, kBankThreads, true, 2 * kBankKT, 255), nr10, kBankThreads, lds, p);
+                else if (bk.real_taps) L(BTGPU_KIN(fmt,pfb100f_kernel, kBankThreads, true, 2 * kBankKT, 7 + 224), nr10, kBankThreads, lds, p);
+                else L(BTGPU_KIN(fmt,pfb100f_kernel, kBankThreads, false, 2 * kBankKT, 3 + 224), nr10, kBankThreads, lds, p);
             }
         } else if (wide) {
             if (bk.real_taps) L(pfb100_kernel<7, 1, NT, true, true, kBankThreadsWide, true>, grid, kBankThreadsWide, lds, p);
             else L(pfb100_kernel<7, 1, NT, false, true, kBankThreadsWide, true>, grid, kBankThreadsWide, lds, p);
         } else {
-            if (bk.real_taps) L(BTGPU_KIN(s16, pfb100_kernel, 7, 1, NT, true, true, kBankThreads, true), grid, kBankThreads, lds, p);
-            else L(BTGPU_KIN(s16, pfb100_kernel, 7, 1, NT, false, true, kBankThreads, true), grid, kBankThreads, lds, p);
+            if (bk.real_taps) L(BTGPU_KIN(fmt,pfb100_kernel, 7, 1, NT, true, true, kBankThreads, true), grid, kBankThreads, lds, p);
+            else L(BTGPU_KIN(fmt,pfb100_kernel, 7, 1, NT, false, true, kBankThreads, true), grid, kBankThreads, lds, p);
         }
     } else {
         p.b2map = b.b2map_ch;
         const size_t lds = bank_lds_bytes(bk.D * (NT - 1) + bk.Q * 100, NT, NT, true);
-        if (bk.real_taps) L(BTGPU_KIN(s16, pfb100_kernel, 7, 1, NT, true, true, kBankThreads, false), p.ntiles, kBankThreads, lds, p);
-        else L(BTGPU_KIN(s16, pfb100_kernel, 7, 1, NT, false, true, kBankThreads, false), p.ntiles, kBankThreads, lds, p);
+        if (bk.real_taps) L(BTGPU_KIN(fmt,pfb100_kernel, 7, 1, NT, true, true, kBankThreads, false), p.ntiles, kBankThreads, lds, p);
+        else L(BTGPU_KIN(fmt,pfb100_kernel, 7, 1, NT, false, true, kBankThreads, false), p.ntiles, kBankThreads, lds, p);
     }
     return p.ntiles;
 }
@@ -179,7 +177,7 @@ inline int launch_channel_bank(const Design &des, const FastPath &fp, bool fuse_
 // Stand-alone noise stage 1 as a polyphase bank (staged squelch without the fused kernel)
 template <class Launcher>
 inline void launch_noise_bank(const Design &des, const FastPath &fp, const BankBuffers &b, size_t x_len,
-                              long long w0, int S, Launcher &&L, bool s16 = false)
+                              long long w0, int S, Launcher &&L, int fmt = 0)
 {
     const btgpu_design &d = des.d;
     const NoiseStage &ns = fp.noise;
@@ -197,7 +195,7 @@ inline void launch_noise_bank(const Design &des, const FastPath &fp, const BankB
     p.Z = b.Z; p.zstride = b.zstride;
     p.b2map = b.b2map_noise;
     const size_t lds = bank_lds_bytes(bk.D * (NT - 1) + bk.Q * 100, NT, NT, false);
-    L(BTGPU_KIN(s16, pfb100_kernel, 15, 5, NT, false, false, kBankThreads, false), p.ntiles, kBankThreads, lds, p);
+    L(BTGPU_KIN(fmt,pfb100_kernel, 15, 5, NT, false, false, kBankThreads, false), p.ntiles, kBankThreads, lds, p);
 }
 
 // Parameters of window_kernel / finish_kernel for a batch of S slots (nb energy blocks per channel, d rows ystride
@@ -352,7 +350,7 @@ inline bool pfbm_fuse_noise(const Design &des, const FastPath &fp, int S, long l
 }
 template <class Launcher>
 inline int launch_channel_bank_m(const Design &des, const FastPath &fp, const BankBuffers &b, size_t x_len,
-                                 long long w0, long long G, Launcher &&L, int fuse_S = 0, bool s16 = false)
+                                 long long w0, long long G, Launcher &&L, int fuse_S = 0, int fmt = 0)
 {
     const btgpu_design &d = des.d;
     const PfbBank &bk = fp.channel;
@@ -389,7 +387,7 @@ inline int launch_channel_bank_m(const Design &des, const FastPath &fp, const Ba
         p.n_T = (long long)ns.outs * (fuse_S - 1) + ns.nw + ns.L3 - 1;
         p.n_taps = b.taps_n; p.n_krot = b.krot_n; p.n_Z = b.Z; p.n_zstride = b.zstride;
         lds = pfbm_lds_bytes(bk.M, bk.D, bk.Q, nch, true, p.stage_len);
-        L(BTGPU_KIN(s16, pfbm_kernel, false, true, 8, 7, true, true), p.ntiles, kPfbmThreads, lds, p);
+        L(BTGPU_KIN(fmt,pfbm_kernel, false, true, 8, 7, true, true), p.ntiles, kPfbmThreads, lds, p);
         if (n_first > 0) {
             // the stage-1 instants in front of tile 0's: one or two tiles of the stand-alone form
             PfbmParams q{};
@@ -400,22 +398,22 @@ inline int launch_channel_bank_m(const Design &des, const FastPath &fp, const Ba
             q.krot = b.krot_n; q.rot_period = nk.rot_period;
             q.ntiles = (int)((q.T + q.TT - 1) / q.TT);
             q.Z = b.Z; q.zstride = b.zstride;
-            L(BTGPU_KIN(s16, pfbm_kernel, false, false, 8, 15, true, false), q.ntiles, kPfbmThreads, pfbm_lds_bytes(nk.M, nk.D, nk.Q, nch, false), q);
+            L(BTGPU_KIN(fmt,pfbm_kernel, false, false, 8, 15, true, false), q.ntiles, kPfbmThreads, pfbm_lds_bytes(nk.M, nk.D, nk.Q, nch, false), q);
         }
         return p.ntiles;
     }
-    if (f8 && bk.Q == 7 && !bk.real_taps) L(BTGPU_KIN(s16, pfbm_kernel, false, true, 8, 7, true, false), p.ntiles, kPfbmThreads, lds, p);          // C8: half-MHz grid
-    else if (f8 && bk.Q == 7) L(BTGPU_KIN(s16, pfbm_kernel, true, true, 8, 7, true, false), p.ntiles, kPfbmThreads, lds, p);
-    else if (bk.M == 8 && bk.Q == 7 && !bk.real_taps) L(BTGPU_KIN(s16, pfbm_kernel, false, true, 8, 7, false, false), p.ntiles, kPfbmThreads, lds, p);
-    else if (bk.M == 20 && bk.Q == 7 && bk.real_taps) L(BTGPU_KIN(s16, pfbm_kernel, true, true, 20, 7, false, false), p.ntiles, kPfbmThreads, lds, p);
-    else if (bk.real_taps) L(BTGPU_KIN(s16, pfbm_kernel, true, true, 0, 0, false, false), p.ntiles, kPfbmThreads, lds, p);
-    else L(BTGPU_KIN(s16, pfbm_kernel, false, true, 0, 0, false, false), p.ntiles, kPfbmThreads, lds, p);
+    if (f8 && bk.Q == 7 && !bk.real_taps) L(BTGPU_KIN(fmt,pfbm_kernel, false, true, 8, 7, true, false), p.ntiles, kPfbmThreads, lds, p);          // C8: half-MHz grid
+    else if (f8 && bk.Q == 7) L(BTGPU_KIN(fmt,pfbm_kernel, true, true, 8, 7, true, false), p.ntiles, kPfbmThreads, lds, p);
+    else if (bk.M == 8 && bk.Q == 7 && !bk.real_taps) L(BTGPU_KIN(fmt,pfbm_kernel, false, true, 8, 7, false, false), p.ntiles, kPfbmThreads, lds, p);
+    else if (bk.M == 20 && bk.Q == 7 && bk.real_taps) L(BTGPU_KIN(fmt,pfbm_kernel, true, true, 20, 7, false, false), p.ntiles, kPfbmThreads, lds, p);
+    else if (bk.real_taps) L(BTGPU_KIN(fmt,pfbm_kernel, true, true, 0, 0, false, false), p.ntiles, kPfbmThreads, lds, p);
+    else L(BTGPU_KIN(fmt,pfbm_kernel, false, true, 0, 0, false, false), p.ntiles, kPfbmThreads, lds, p);
     return p.ntiles;
 }
 
 template <class Launcher>
 inline void launch_noise_bank_m(const Design &des, const FastPath &fp, const BankBuffers &b, size_t x_len,
-                                long long w0, int S, Launcher &&L, bool s16 = false)
+                                long long w0, int S, Launcher &&L, int fmt = 0)
 {
     const btgpu_design &d = des.d;
     const NoiseStage &ns = fp.noise;
@@ -431,9 +429,9 @@ inline void launch_noise_bank_m(const Design &des, const FastPath &fp, const Ban
     p.ntiles = (int)((Tn + p.TT - 1) / p.TT);
     p.Z = b.Z; p.zstride = b.zstride;
     const size_t lds = pfbm_lds_bytes(bk.M, bk.D, bk.Q, nch, false);
-    if (bk.natural && bk.M == 8 && nch == 8 && bk.Q == 15) L(BTGPU_KIN(s16, pfbm_kernel, false, false, 8, 15, true, false), p.ntiles, kPfbmThreads, lds, p);
-    else if (bk.M == 8 && bk.Q == 15) L(BTGPU_KIN(s16, pfbm_kernel, false, false, 8, 15, false, false), p.ntiles, kPfbmThreads, lds, p);
-    else L(BTGPU_KIN(s16, pfbm_kernel, false, false, 0, 0, false, false), p.ntiles, kPfbmThreads, lds, p);
+    if (bk.natural && bk.M == 8 && nch == 8 && bk.Q == 15) L(BTGPU_KIN(fmt,pfbm_kernel, false, false, 8, 15, true, false), p.ntiles, kPfbmThreads, lds, p);
+    else if (bk.M == 8 && bk.Q == 15) L(BTGPU_KIN(fmt,pfbm_kernel, false, false, 8, 15, false, false), p.ntiles, kPfbmThreads, lds, p);
+    else L(BTGPU_KIN(fmt,pfbm_kernel, false, false, 0, 0, false, false), p.ntiles, kPfbmThreads, lds, p);
 }
 
 }  // namespace btgpu

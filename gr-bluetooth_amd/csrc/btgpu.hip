@@ -19,6 +19,9 @@
 #include "payload_sweep.hip.h"
 #include "pfb100.hip.h"
 #include "s16_inst.h"        // the int16-input kernels: declared here, compiled in s16_kernels.hip
+#include "s8_inst.h"         // the int8-input kernels: declared here, compiled in s8_kernels.hip
+
+static inline size_t in_sample_bytes(int fmt) { return fmt == btgpu::kInS8 ? 2 : fmt == btgpu::kInS16 ? 4 : 8; }   // bytes per complex sample
 #include "bank_launch.h"
 #include "hopseq.hip.h"
 
@@ -114,7 +117,7 @@ struct btgpu_handle {
     bool no_nsym = false;            // BTGPU_FLAG_NO_NSYM: skip the M&M continuation that produces hit.nsym
     int verify = 0;                  // exact rows under the polyphase path's records (exact.hip.h): 0 off, 1 presence + uncovered hits, 2 uncovered hits only
     int vcap = 0, bm_tiles = 0;
-    ExactRowsKernel ex_kern = nullptr, ex_kern_s16 = nullptr; size_t ex_lds = 0;   // exact rows on a float / an int16 input stream
+    ExactRowsKernel ex_kern = nullptr, ex_kern_s16 = nullptr, ex_kern_s8 = nullptr; size_t ex_lds = 0;   // exact rows on a float / an int16 / an int8 input stream
     bool exact_all = false;          // BTGPU_FLAG_EXACT_ALL: every row of every channel is recomputed (no presence)
     std::vector<const void *> lds_opted;   // bank kernels that have been granted > 48 KiB of dynamic LDS on this handle's device
     DevBuf d_tapsA;                  // the direct-form channel bank's taps as exact_rows_kernel's A operand (exact_pack_taps)
@@ -295,11 +298,11 @@ struct btgpu_handle {
     hipEvent_t ev_vdone[2] = {nullptr, nullptr};      // the batch's tail (whose exact stage re-reads the input) has left the tail stream
     bool stage_used[2] = {false, false};
     unsigned stage_turn = 0;
-    // s16: the input format of this call -- interleaved int16 (4 bytes per complex sample) instead of float32.  A property of
-    // the CALL, not of the handle: it picks the kernels' int16 instantiations and halves the bytes staged; `head` is float always.
+    // fmt: the input format of this call (kernels.hip.h InFmt) -- interleaved int16 or int8 (4 or 2 bytes per complex sample) instead of
+    // float32.  A property of the CALL, not of the handle: it picks the kernels' instantiations and sizes the bytes staged; `head` is float always.
     int stage_batch(const float *head, size_t n_head_zero, const void *body, size_t n_body, long long w0,
-                    uint64_t abs_first_slot, int S, bool s16 = false);
-    int process_batch(const float2 *d_x, size_t x_len, long long w0, uint64_t abs_first_slot, int S, hipStream_t st, bool s16 = false);
+                    uint64_t abs_first_slot, int S, int fmt = kInF32);
+    int process_batch(const float2 *d_x, size_t x_len, long long w0, uint64_t abs_first_slot, int S, hipStream_t st, int fmt = kInF32);
     int harvest(TailCtx &t);
     int harvest_all(bool block);
 };
@@ -308,7 +311,7 @@ struct btgpu_handle {
 // one batch of S slots; d_x[w0] = first sample of window 0 of the batch, d_x[0..w0) = margin
 // ---------------------------------------------------------------------------------------
 int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, uint64_t abs_first_slot,
-                                int S, hipStream_t st, bool s16)
+                                int S, hipStream_t st, int fmt)
 {
     const btgpu_design &d = des.d;
     const int nch = d.high_channel - d.low_channel + 1;
@@ -339,7 +342,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
     if (verify) HIPCHK(this, hipMemsetAsync(t.d_vcount.p, 0, kVerCountWords * sizeof(unsigned int), st));
     HIPCHK(this, mark(0, st));
     int ntiles = 0, tiles_per_block = 1, tail_tiles = 0;
-    const auto ddc = s16 ? ddc_direct_kernel_s16<2> : ddc_direct_kernel<2>;   // the direct-form bank for this call's input format
+    const auto ddc = BTGPU_KIN(fmt, ddc_direct_kernel, 2);   // the direct-form bank for this call's input format
     bool fused_m = false;                                       // small-M banks: stage 1 ran inside the channel bank's kernel
     // ... and its matrix-pipe form (ddc_mfma.hip.h): tiles of 128 outputs of one segment, row blocks in groups of kDmRB
     auto launch_ddc_mfma = [&](const FilterBank &fb, const DevBuf &tp, int qc, long long first, const DevBuf &rot, const DevBuf &rotstep,
@@ -351,7 +354,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
         m.Y = Y; m.G = Gout; m.ystride = ys; m.nch = nch; m.seg_len = seg_len; m.seg_stride = seg_stride;
         const unsigned gx = seg_len ? (unsigned)(((seg_len + kDmCols - 1) / kDmCols) * S) : (unsigned)((Gout + kDmCols - 1) / kDmCols);
         const dim3 grid(gx, (unsigned)((exact_dense_blocks(nch) + kDmRB - 1) / kDmRB));
-        hipLaunchKernelGGL(s16 ? ddc_mfma_kernel_s16<0> : ddc_mfma_kernel, grid, dim3(kDmThreads), ddc_mfma_lds_bytes(m.D, qc), st, m);
+        hipLaunchKernelGGL(fmt == kInS8 ? ddc_mfma_kernel_s8<0> : fmt == kInS16 ? ddc_mfma_kernel_s16<0> : ddc_mfma_kernel, grid, dim3(kDmThreads), ddc_mfma_lds_bytes(m.D, qc), st, m);
     };
 
     // ---- channel bank -> demodulated stream d[g][nch] + |Y|^2 tile sums (polyphase) or block sums P, Pt (direct) ----
@@ -365,7 +368,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
     };
     if (use_pfb && pfb_g) {
         BankBuffers bb = bank_buffers(d_x, t);
-        ntiles = launch_channel_bank_g(des, fp, bb, (const float4 *)d_arows_ch.p, x_len, w0, G, Lg, s16);
+        ntiles = launch_channel_bank_g(des, fp, bb, (const float4 *)d_arows_ch.p, x_len, w0, G, Lg, fmt);
         tiles_per_block = ops / pfbm_tile(fp.channel.M); tail_tiles = des.tail / pfbm_tile(fp.channel.M);
         HIPCHK(this, mark(1, st));
     } else if (use_pfb && pfb_small) {
@@ -377,7 +380,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
         // whole GPU suite has run with it: bit-identical outputs under the emulator and in the 8 Msps GPU tests, profiles/r04_v_*
         static const bool fuse_m_on = getenv("BTGPU_C8_FUSE") && atoi(getenv("BTGPU_C8_FUSE")) == 1;
         fused_m = fuse_m_on && use_staged && noise_small && pfbm_fuse_noise(des, fp, S, G, drow);
-        ntiles = launch_channel_bank_m(des, fp, bb, x_len, w0, G, L, fused_m ? S : 0, s16);
+        ntiles = launch_channel_bank_m(des, fp, bb, x_len, w0, G, L, fused_m ? S : 0, fmt);
         tiles_per_block = ops / pfbm_tile(fp.channel.M); tail_tiles = des.tail / pfbm_tile(fp.channel.M);
         HIPCHK(this, mark(1, st));
     } else if (use_pfb) {
@@ -406,7 +409,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
                    v == "run512" ? (int)kBankRun512 : v == "run512r" ? (int)kBankRun512r : v == "run256d" ? (int)kBankRun256d :
                    v == "run256e" ? (int)kBankRun256e : v == "run256a" ? (int)kBankRun256a : (int)kBankRun256;
         }();
-        ntiles = launch_channel_bank(des, fp, fuse_noise, bb, x_len, w0, S, G, nb, L, variant, s16);
+        ntiles = launch_channel_bank(des, fp, fuse_noise, bb, x_len, w0, S, G, nb, L, variant, fmt);
         tiles_per_block = ops / TT; tail_tiles = des.tail / TT;
         HIPCHK(this, mark(1, st));
     } else {
@@ -443,16 +446,16 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
             auto L = [&](void (*kern)(PfbParams), int grid, int threads, size_t lds, const PfbParams &p) {
                 hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)threads), lds, st, p);
             };
-            launch_noise_bank(des, fp, bb, x_len, w0, S, L, s16);
+            launch_noise_bank(des, fp, bb, x_len, w0, S, L, fmt);
         } else if (noise_g) {
             BankBuffers bb = bank_buffers(d_x, t);
-            launch_noise_bank_g(des, fp, bb, (const float4 *)d_arows_n.p, x_len, w0, S, Lg, s16);
+            launch_noise_bank_g(des, fp, bb, (const float4 *)d_arows_n.p, x_len, w0, S, Lg, fmt);
         } else if (noise_small) {
             BankBuffers bb = bank_buffers(d_x, t);
             auto L = [&](void (*kern)(PfbmParams), int grid, int threads, size_t lds, const PfbmParams &p) {
                 hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)threads), lds, st, p);
             };
-            launch_noise_bank_m(des, fp, bb, x_len, w0, S, L, s16);
+            launch_noise_bank_m(des, fp, bb, x_len, w0, S, L, fmt);
         } else {
             // stage 1 as a direct-form bank: B-spline prototype (a few hundred taps at most), hop R
             const LaunchShape &s = shape_s1;
@@ -518,7 +521,7 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
     auto launch_exact_rows = [&](const uint32_t *bitmap, unsigned int *stat, hipStream_t s_) {
         const ExactParams ep = make_exact_params(des, x_len, w0, G, (const float *)d_tapsA.p, (const float2 *)d_rot_ch.p, (const float *)d_atan.p,
                                                  bitmap, vb.bm_tiles, (float *)d_d.p, drow, (float *)(use_dcol ? t.d_dcol.p : nullptr), stat, (const float *)d_tapsD.p);
-        hipLaunchKernelGGL(s16 ? ex_kern_s16 : ex_kern, dim3((unsigned)vb.bm_tiles), dim3(kExThreads), ex_lds, s_, ep, d_x);
+        hipLaunchKernelGGL(fmt == kInS8 ? ex_kern_s8 : fmt == kInS16 ? ex_kern_s16 : ex_kern, dim3((unsigned)vb.bm_tiles), dim3(kExThreads), ex_lds, s_, ep, d_x);
     };
     if (verify && exact_all) {
         hipLaunchKernelGGL(exact_mark_all_kernel, dim3((unsigned)((vb.bm_tiles * kExBmWords + 255) / 256)), dim3(256), 0, ps, vb.bm1, vb.bm_tiles, nch);
@@ -695,12 +698,13 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
 // kernels.  `head` (may be null) supplies real samples for the first n_head samples instead of zeros when the
 // caller has them (the margin carried between btgpu_work calls).  Buffers alternate; a buffer is reused only
 // after the batch that read it has left the main stream.
-// int16 input (s16): the same two pinned and two device buffers, at 4 bytes per complex sample instead of 8; `head` stays float
-// (the margin carried between work calls is kept widened) and is narrowed back here -- exact for what an int16 call left there.
+// int16 / int8 input (fmt): the same two pinned and two device buffers, at 4 / 2 bytes per complex sample instead of 8 -- every host
+// and PCIe copy is sized in bytes of the call's format; `head` stays float (the margin carried between work calls is kept widened)
+// and is narrowed back here, saturating -- exact for what a call of the same or a narrower format left there.
 int btgpu_handle::stage_batch(const float *head, size_t n_head, const void *body, size_t n_body, long long w0,
-                              uint64_t abs_first_slot, int S, bool s16)
+                              uint64_t abs_first_slot, int S, int fmt)
 {
-    const size_t ssz = s16 ? 2 * sizeof(int16_t) : sizeof(float2);              // bytes per complex sample
+    const size_t ssz = in_sample_bytes(fmt);                                     // bytes per complex sample
     const unsigned k = stage_turn++ & 1u;
     const size_t cap = in_cap + (size_t)margin + 64;
     if (n_head + n_body > cap) { set_error("staging overflow"); return BTGPU_EINVAL; }
@@ -719,11 +723,14 @@ int btgpu_handle::stage_batch(const float *head, size_t n_head, const void *body
     }
     char *dst = (char *)h_stage[k];
     if (n_head) {
-        if (head && s16) {
+        if (head && fmt == kInS16) {
             int16_t *d16 = (int16_t *)dst;
             for (size_t i = 0; i < 2 * n_head; i++) d16[i] = (int16_t)std::lrintf(std::min(32767.f, std::max(-32768.f, head[i])));
+        } else if (head && fmt == kInS8) {
+            int8_t *d8 = (int8_t *)dst;
+            for (size_t i = 0; i < 2 * n_head; i++) d8[i] = (int8_t)std::lrintf(std::min(127.f, std::max(-128.f, head[i])));
         } else if (head) std::memcpy(dst, head, n_head * ssz);
-        else std::memset(dst, 0, n_head * ssz);                                  // (int16 zeros are zero bytes too)
+        else std::memset(dst, 0, n_head * ssz);                                  // (integer zeros are zero bytes too)
     }
     char *d_buf = (char *)(k == 0 ? d_in.p : d_in_b.p);
     // A caller's buffer that is page-locked already (hipHostMalloc / hipHostRegister: what a block can do once with the
@@ -765,7 +772,7 @@ int btgpu_handle::stage_batch(const float *head, size_t n_head, const void *body
     }
     HIPCHK(this, hipEventRecord(ev_copied[k], copy_stream));
     HIPCHK(this, hipStreamWaitEvent(stream, ev_copied[k], 0));
-    const int rc = process_batch((const float2 *)d_buf, n_head + n_body, w0, abs_first_slot, S, stream, s16);
+    const int rc = process_batch((const float2 *)d_buf, n_head + n_body, w0, abs_first_slot, S, stream, fmt);
     // (behind the enqueue: the kernels queue up under the copy; also where process_batch failed -- the buffer is the caller's again
     // only once the copy has left it)
     if (direct) { const hipError_t se = hipEventSynchronize(ev_copied[k]); if (rc != BTGPU_OK) return rc; HIPCHK(this, se); }
@@ -1350,7 +1357,7 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
     TRY(h->alloc(h->d_winbits, (size_t)((S + 2) / 3) * kBitWords * kWinThreads * sizeof(uint32_t)));   // most workgroups: 3 slots each
     if (h->verify) {
         h->vcap = verify_capacity(S, nch);
-        h->ex_kern = exact_rows_pick(d.decimation); h->ex_kern_s16 = exact_rows_pick<true>(d.decimation); h->ex_lds = exact_lds_bytes(d.decimation);
+        h->ex_kern = exact_rows_pick(d.decimation); h->ex_kern_s16 = exact_rows_pick<kInS16>(d.decimation); h->ex_kern_s8 = exact_rows_pick<kInS8>(d.decimation); h->ex_lds = exact_lds_bytes(d.decimation);
         // Which form (exact_dense.hip.h): dense where no sparse kernel is instantiated, on BTGPU_FLAG_EXACT_DENSE and on
         // BTGPU_EXACT_FORM=dense; BTGPU_EXACT_FORM=sparse asks for the sparse form wherever it exists (A/B timing).  Otherwise
         // sparse -- under BTGPU_FLAG_EXACT_ALL too: profiles/exact_dense_ab.json
@@ -1363,7 +1370,7 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
             std::vector<float> td(exact_dense_taps_floats(nch, d.decimation));
             exact_pack_taps_dense(des.channel.taps.data(), nch, des.channel.ntp, d.decimation, td.data());
             TRY(h->upload(h->d_tapsD, td.data(), td.size() * sizeof(float)));
-            h->ex_kern = exact_dense_kernel; h->ex_kern_s16 = exact_dense_kernel_s16<0>; h->ex_lds = exact_dense_lds_bytes(d.decimation);
+            h->ex_kern = exact_dense_kernel; h->ex_kern_s16 = exact_dense_kernel_s16<0>; h->ex_kern_s8 = exact_dense_kernel_s8<0>; h->ex_lds = exact_dense_lds_bytes(d.decimation);
         } else {
             std::vector<float> ta(exact_taps_floats(nch, d.decimation));
             exact_pack_taps(des.channel.taps.data(), nch, des.channel.ntp, d.decimation, ta.data());
@@ -1372,6 +1379,7 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         h->bm_tiles = exact_ntiles(h->ystride + 64);
         (void)hipFuncSetAttribute((const void *)h->ex_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(h->ex_lds, 64 * 1024));
         (void)hipFuncSetAttribute((const void *)h->ex_kern_s16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(h->ex_lds, 64 * 1024));
+        (void)hipFuncSetAttribute((const void *)h->ex_kern_s8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(h->ex_lds, 64 * 1024));
     }
     // Which kernel runs the direct-form banks (ddc_mfma.hip.h): the matrix-pipe form on BTGPU_FLAG_DIRECT_MFMA and on
     // BTGPU_DIRECT_FORM=mfma; BTGPU_DIRECT_FORM=valu asks for the vector-ALU form whatever the flag says (A/B timing).  The same bits
@@ -1404,6 +1412,7 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         // more than 48 KiB of dynamic LDS is an opt-in per kernel
         (void)hipFuncSetAttribute((const void *)ddc_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute((const void *)ddc_mfma_kernel_s16<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void *)ddc_mfma_kernel_s8<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     for (int i = 0; i < h->nctx; i++) {
         auto &t = h->tc[i];
@@ -1489,21 +1498,37 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
     (void)hipFuncSetAttribute((const void *)pfb100f_kernel<kBankThreads, false, 2 * kBankKT, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     // ... and for their int16-input twins (the run kernel's are opted in next to their launch, like the float ones)
     (void)hipFuncSetAttribute((const void *)ddc_direct_kernel_s16<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)ddc_direct_kernel_s8<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<7, 1, 26, true, true, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s8<7, 1, 26, true, true, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<7, 1, 26, false, true, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s8<7, 1, 26, false, true, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<7, 1, 26, true, true, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s8<7, 1, 26, true, true, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<7, 1, 26, false, true, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s8<7, 1, 26, false, true, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     (void)hipFuncSetAttribute((const void *)pfb100_kernel_s16<15, 5, 10, false, false, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfb100_kernel_s8<15, 5, 10, false, false, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, true, 8, 7, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<false, true, 8, 7, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, true, 8, 7, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<false, true, 8, 7, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<true, true, 8, 7, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<true, true, 8, 7, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, true, 8, 7, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<false, true, 8, 7, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<true, true, 20, 7, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<true, true, 20, 7, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<true, true, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<true, true, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, true, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<false, true, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, false, 8, 15, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<false, false, 8, 15, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, false, 8, 15, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<false, false, 8, 15, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     (void)hipFuncSetAttribute((const void *)pfbm_kernel_s16<false, false, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    (void)hipFuncSetAttribute((const void *)pfbm_kernel_s8<false, false, 0, 0, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     h->pre.assign((size_t)h->margin * 2, 0.f);
     if (getenv("BTGPU_VERBOSE"))
         fprintf(stderr, "btgpu_create: %d contexts, d=%p Z=%p ptile=%p; device memory %zu bytes, per context: time-major stream %zu, tile-blocked stream %zu\n",
@@ -1540,13 +1565,14 @@ int btgpu_device_count(void)
 }
 const char *btgpu_last_error(const btgpu_handle *h) { return h ? h->err.c_str() : "null handle"; }
 
-// The three input entries in both formats: s16 = interleaved int16 behind the pointer (4 bytes per complex sample), n in complex
-// samples either way.
+// The three input entries in the three formats: interleaved float32, int16 or int8 behind the pointer (8, 4 or 2 bytes per
+// complex sample), n in complex samples whichever it is.
 static int process_device_any(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
-                              uint64_t first_slot, uint64_t n_slots, void *hip_stream, bool s16)
+                              uint64_t first_slot, uint64_t n_slots, void *hip_stream, int fmt)
 {
     if (!h || !d_iq) return BTGPU_EINVAL;
-    if (s16 && ((uintptr_t)d_iq & 7u)) return BTGPU_EINVAL;      // the banks load int16 samples in aligned pairs (btgpu.h)
+    if (fmt == kInS16 && ((uintptr_t)d_iq & 7u)) return BTGPU_EINVAL;      // the banks load int16 samples in aligned pairs (btgpu.h)
+    if (fmt == kInS8 && ((uintptr_t)d_iq & 3u)) return BTGPU_EINVAL;       // ... and int8 samples in aligned pairs: one 32-bit word
     const btgpu_design &d = h->des.d;
     if (n_slots == 0) return BTGPU_OK;
     const size_t need = left_margin + (size_t)d.history + (size_t)(n_slots - 1) * d.samples_per_slot;
@@ -1557,7 +1583,7 @@ static int process_device_any(btgpu_handle *h, const void *d_iq, size_t n_comple
     for (uint64_t s0 = 0; s0 < n_slots; s0 += (uint64_t)h->max_slots) {
         const int S = (int)std::min<uint64_t>((uint64_t)h->max_slots, n_slots - s0);
         const long long w0 = (long long)left_margin + (long long)s0 * d.samples_per_slot;
-        int rc = h->process_batch((const float2 *)d_iq, n_complex, w0, first_slot + s0, S, st, s16);
+        int rc = h->process_batch((const float2 *)d_iq, n_complex, w0, first_slot + s0, S, st, fmt);
         if (rc == BTGPU_EOVERFLOW) rc_all = rc;
         else if (rc != BTGPU_OK) return rc;
     }
@@ -1566,19 +1592,24 @@ static int process_device_any(btgpu_handle *h, const void *d_iq, size_t n_comple
 int btgpu_process_device(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
                          uint64_t first_slot, uint64_t n_slots, void *hip_stream)
 {
-    return process_device_any(h, d_iq, n_complex, left_margin, first_slot, n_slots, hip_stream, false);
+    return process_device_any(h, d_iq, n_complex, left_margin, first_slot, n_slots, hip_stream, kInF32);
 }
 int btgpu_process_device_s16(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
                              uint64_t first_slot, uint64_t n_slots, void *hip_stream)
 {
-    return process_device_any(h, d_iq, n_complex, left_margin, first_slot, n_slots, hip_stream, true);
+    return process_device_any(h, d_iq, n_complex, left_margin, first_slot, n_slots, hip_stream, kInS16);
+}
+int btgpu_process_device_s8(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
+                            uint64_t first_slot, uint64_t n_slots, void *hip_stream)
+{
+    return process_device_any(h, d_iq, n_complex, left_margin, first_slot, n_slots, hip_stream, kInS8);
 }
 
 static int process_host_any(btgpu_handle *h, const void *iq, size_t n_complex, size_t left_margin, uint64_t first_slot,
-                            uint64_t n_slots, bool s16)
+                            uint64_t n_slots, int fmt)
 {
     if (!h || !iq) return BTGPU_EINVAL;
-    const size_t ssz = s16 ? 2 * sizeof(int16_t) : 2 * sizeof(float);
+    const size_t ssz = in_sample_bytes(fmt);
     const btgpu_design &d = h->des.d;
     if (n_slots == 0) return BTGPU_OK;
     const size_t H = (size_t)d.history, slot = (size_t)d.samples_per_slot, mg = (size_t)h->margin;
@@ -1590,7 +1621,7 @@ static int process_host_any(btgpu_handle *h, const void *iq, size_t n_complex, s
         const size_t seg = H + (size_t)(S - 1) * slot;
         const size_t i0 = left_margin + (size_t)s0 * slot;           // sample index of window 0 of this batch
         const size_t have = std::min(mg, i0), zeros = mg - have;     // real samples in front, else implied zeros
-        int rc = h->stage_batch(nullptr, zeros, (const char *)iq + (i0 - have) * ssz, have + seg, (long long)mg, first_slot + s0, S, s16);
+        int rc = h->stage_batch(nullptr, zeros, (const char *)iq + (i0 - have) * ssz, have + seg, (long long)mg, first_slot + s0, S, fmt);
         if (rc == BTGPU_EOVERFLOW) rc_all = rc;
         else if (rc != BTGPU_OK) return rc;
     }
@@ -1599,19 +1630,24 @@ static int process_host_any(btgpu_handle *h, const void *iq, size_t n_complex, s
 int btgpu_process_host(btgpu_handle *h, const float *iq, size_t n_complex, size_t left_margin, uint64_t first_slot,
                        uint64_t n_slots)
 {
-    return process_host_any(h, iq, n_complex, left_margin, first_slot, n_slots, false);
+    return process_host_any(h, iq, n_complex, left_margin, first_slot, n_slots, kInF32);
 }
 int btgpu_process_host_s16(btgpu_handle *h, const int16_t *iq, size_t n_complex, size_t left_margin, uint64_t first_slot,
                            uint64_t n_slots)
 {
-    return process_host_any(h, iq, n_complex, left_margin, first_slot, n_slots, true);
+    return process_host_any(h, iq, n_complex, left_margin, first_slot, n_slots, kInS16);
+}
+int btgpu_process_host_s8(btgpu_handle *h, const int8_t *iq, size_t n_complex, size_t left_margin, uint64_t first_slot,
+                          uint64_t n_slots)
+{
+    return process_host_any(h, iq, n_complex, left_margin, first_slot, n_slots, kInS8);
 }
 
-static int work_any(btgpu_handle *h, const void *items_, size_t n_items, size_t *consumed, bool s16)
+static int work_any(btgpu_handle *h, const void *items_, size_t n_items, size_t *consumed, int fmt)
 {
     if (!h || !items_) return BTGPU_EINVAL;
-    const size_t ssz = s16 ? 2 * sizeof(int16_t) : 2 * sizeof(float);
-    const float *items = (const float *)items_; const int16_t *items16 = (const int16_t *)items_;
+    const size_t ssz = in_sample_bytes(fmt);
+    const float *items = (const float *)items_; const int16_t *items16 = (const int16_t *)items_; const int8_t *items8 = (const int8_t *)items_;
     const btgpu_design &d = h->des.d;
     if (consumed) *consumed = 0;
     const size_t H = (size_t)d.history, slot = (size_t)d.samples_per_slot, mg = (size_t)h->margin;
@@ -1627,7 +1663,7 @@ static int work_any(btgpu_handle *h, const void *items_, size_t n_items, size_t 
         size_t from_items = std::min(mg, i0), from_pre = mg - from_items;
         // pre holds the mg samples before items[0]; its last from_pre samples come first
         int rc = h->stage_batch(from_pre ? h->pre.data() + 2 * (mg - from_pre) : nullptr, from_pre,
-                                (const char *)items_ + (i0 - from_items) * ssz, from_items + seg, (long long)mg, h->push_slot + s0, S, s16);
+                                (const char *)items_ + (i0 - from_items) * ssz, from_items + seg, (long long)mg, h->push_slot + s0, S, fmt);
         if (rc == BTGPU_EOVERFLOW) rc_all = rc;
         else if (rc != BTGPU_OK) return rc;
     }
@@ -1637,7 +1673,8 @@ static int work_any(btgpu_handle *h, const void *items_, size_t n_items, size_t 
         std::vector<float> np(2 * mg);
         for (size_t i = 0; i < mg; i++) {
             long long src = (long long)used - (long long)mg + (long long)i;      // item index, may be < 0 -> old pre
-            if (src >= 0 && s16) { np[2 * i] = (float)items16[2 * src]; np[2 * i + 1] = (float)items16[2 * src + 1]; continue; }   // (kept widened: exact)
+            if (src >= 0 && fmt == kInS8) { np[2 * i] = (float)items8[2 * src]; np[2 * i + 1] = (float)items8[2 * src + 1]; continue; }
+            if (src >= 0 && fmt == kInS16) { np[2 * i] = (float)items16[2 * src]; np[2 * i + 1] = (float)items16[2 * src + 1]; continue; }   // (kept widened: exact)
             const float *pp = src >= 0 ? items + 2 * src : h->pre.data() + 2 * (mg + src);
             np[2 * i] = pp[0]; np[2 * i + 1] = pp[1];
         }
@@ -1646,8 +1683,9 @@ static int work_any(btgpu_handle *h, const void *items_, size_t n_items, size_t 
     if (consumed) *consumed = used;
     return rc_all;
 }
-int btgpu_work(btgpu_handle *h, const float *items, size_t n_items, size_t *consumed) { return work_any(h, items, n_items, consumed, false); }
-int btgpu_work_s16(btgpu_handle *h, const int16_t *items, size_t n_items, size_t *consumed) { return work_any(h, items, n_items, consumed, true); }
+int btgpu_work(btgpu_handle *h, const float *items, size_t n_items, size_t *consumed) { return work_any(h, items, n_items, consumed, kInF32); }
+int btgpu_work_s16(btgpu_handle *h, const int16_t *items, size_t n_items, size_t *consumed) { return work_any(h, items, n_items, consumed, kInS16); }
+int btgpu_work_s8(btgpu_handle *h, const int8_t *items, size_t n_items, size_t *consumed) { return work_any(h, items, n_items, consumed, kInS8); }
 
 int btgpu_push(btgpu_handle *h, const float *iq, size_t n_complex)
 {

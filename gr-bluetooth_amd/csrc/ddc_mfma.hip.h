@@ -21,7 +21,7 @@
 // CHUNKS of QC <= 16 blocks; a chunk needs the 127 + QC columns [q0, q0 + QC + 127), which is the ring: column m lives in slot
 // m % (127 + QC), in exact_dense's conflict-free layout [column][re | im][r] with the column stride 2 dpad + 4 floats.  Going to
 // the next chunk retires QC columns and brings QC new ones into the very slots retired: their samples are loaded into registers
-// (raw, i.e. 4 bytes per int16 sample; kDmPF per lane, all in flight at once) when the current chunk BEGINS and are written to LDS
+// (raw, i.e. 4 bytes per int16 sample, 2 per int8 sample; kDmPF per lane, all in flight at once) when the current chunk BEGINS and are written to LDS
 // between two barriers when it ends -- QC NI nblk 4 matrix instructions later.  61.8 KB at D = 50: two workgroups per CU.
 // Outside the input (a < 0, a >= x_len) the samples are zeros, the loads clamped, as in the VALU form.
 // (Single samples, not InPiece pairs: a column's first sample has either parity (odd D, odd `first`), and the float stream's
@@ -83,18 +83,21 @@ inline int ddc_mfma_chunk(int D, int NB)
     return qc;
 }
 
-template <bool S16> struct DmRaw { typedef float2 type; };
-template <> struct DmRaw<true> { typedef uint32_t type; };
-template <bool S16>
-__device__ __forceinline__ typename DmRaw<S16>::type dm_load_raw(const float2 *x, long long i)
+template <int FMT> struct DmRaw { typedef float2 type; };
+template <> struct DmRaw<kInS16> { typedef uint32_t type; };
+template <> struct DmRaw<kInS8> { typedef uint16_t type; };      // one int8 sample: a 16-bit load, one register where the float form takes two
+template <int FMT>
+__device__ __forceinline__ typename DmRaw<FMT>::type dm_load_raw(const float2 *x, long long i)
 {
-    if constexpr (S16) return ((const uint32_t *)x)[i];
+    if constexpr (FMT == kInS16) return ((const uint32_t *)x)[i];
+    else if constexpr (FMT == kInS8) return ((const uint16_t *)x)[i];
     else return x[i];
 }
 __device__ __forceinline__ float2 dm_widen(const float2 &v) { return v; }
 __device__ __forceinline__ float2 dm_widen(uint32_t w) { return s16_widen(w); }
+__device__ __forceinline__ float2 dm_widen(uint16_t h) { return s8_widen(h); }
 
-template <bool S16>
+template <int FMT>
 __device__ __forceinline__ void ddc_mfma_body(const DdcMfmaParams &p)
 {
 #pragma clang fp contract(off)
@@ -125,10 +128,10 @@ __device__ __forceinline__ void ddc_mfma_body(const DdcMfmaParams &p)
         const bool inside = base >= 0 && base + total <= p.x_len;  // uniform
         for (int s = tid; s < total; s += kDmThreads) {
             float2 v;
-            if (inside) v = load_sample<S16>(p.x, base + s);
+            if (inside) v = load_sample<FMT>(p.x, base + s);
             else {
                 const long long a = base + s;
-                v = load_sample<S16>(p.x, a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1));
+                v = load_sample<FMT>(p.x, a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1));
                 if (!(a >= 0 && a < p.x_len)) v = make_float2(0.f, 0.f);
             }
             Bs[m * CS + r] = v.x;
@@ -138,13 +141,13 @@ __device__ __forceinline__ void ddc_mfma_body(const DdcMfmaParams &p)
         }
     }
     // ---- the ring: the chunk that starts at tap block q1 brings the columns [q1 + 127, q1 + 127 + nq1) ----
-    typename DmRaw<S16>::type raw[kDmPF];
+    typename DmRaw<FMT>::type raw[kDmPF];
     auto prefetch = [&](int q1) {
         const long long a0 = base + (long long)(q1 + kDmCols - 1) * D + tid;
 #pragma unroll
         for (int k = 0; k < kDmPF; k++) {                          // unconditional, clamped: all in flight together
             const long long a = a0 + k * kDmThreads;
-            raw[k] = dm_load_raw<S16>(p.x, a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1));
+            raw[k] = dm_load_raw<FMT>(p.x, a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1));
         }
     };
     auto commit = [&](int q1) {
@@ -277,9 +280,11 @@ __device__ __forceinline__ void ddc_mfma_body(const DdcMfmaParams &p)
     }
 }
 
-__global__ __launch_bounds__(kDmThreads, 2) void ddc_mfma_kernel(DdcMfmaParams p) { ddc_mfma_body<false>(p); }
+__global__ __launch_bounds__(kDmThreads, 2) void ddc_mfma_kernel(DdcMfmaParams p) { ddc_mfma_body<kInF32>(p); }
 // (a template only so that it can be instantiated in the int16 kernels' translation unit: s16_inst.h)
 template <int V = 0>
-__global__ __launch_bounds__(kDmThreads, 2) void ddc_mfma_kernel_s16(DdcMfmaParams p) { ddc_mfma_body<true>(p); }
+__global__ __launch_bounds__(kDmThreads, 2) void ddc_mfma_kernel_s16(DdcMfmaParams p) { ddc_mfma_body<kInS16>(p); }
+template <int V = 0>
+__global__ __launch_bounds__(kDmThreads, 2) void ddc_mfma_kernel_s8(DdcMfmaParams p) { ddc_mfma_body<kInS8>(p); }
 
 }  // namespace btgpu

@@ -143,7 +143,10 @@ constexpr bool exact_full_a(int D) { return BTGPU_EX_FULLA && D > 25; }
 // (3) the wide form was tried on the float stream (16-byte loads, the lane keeps its half) and measured the same
 // (profiles/r06_u_*): what bounds this load is the number of lanes' addresses the texture unit walks, and both half-waves
 // of a 2-byte load fall into the same 64-byte lines.  The clamped edge branch widens whole samples one by one.
-template <int D, bool S16>
+// int8 (FMT = kInS8): the same choice one size down -- D SIGNED 1-BYTE LOADS (global_load_sbyte) at a 2-byte stride, each followed
+// by one conversion.  A byte load asks no alignment at all, so a column that starts at an odd sample (odd D, odd first0) needs no
+// head or tail; a wave's span of 32 D samples is 64 D bytes, one to fifty 64-byte lines that its two half-waves share.
+template <int D, int FMT>
 __device__ __forceinline__ void exact_rows_body(const ExactParams &p, const float2 *__restrict__ x)
 {
     HIP_DYNAMIC_SHARED(float2, lds)
@@ -186,10 +189,14 @@ __device__ __forceinline__ void exact_rows_body(const ExactParams &p, const floa
             if (sb >= 0 && sb + NS <= p.x_len) {                   // uniform: the wave's span lies inside the stream
                 // (16-byte loads -- two samples, the lane keeps its half -- cost the texture unit a quarter of this form's work per tile and
                 // measured the same: 2.09 ms against 2.07, profiles/r06_u_*)
-                if constexpr (S16) {
+                if constexpr (FMT == kInS16) {
                     const int16_t *xh = (const int16_t *)x + 2 * s0 + (lane >> 5);
 #pragma unroll
                     for (int r = 0; r < D; r++) B[r] = (float)xh[2 * r];
+                } else if constexpr (FMT == kInS8) {
+                    const int8_t *xb = (const int8_t *)x + 2 * s0 + (lane >> 5);
+#pragma unroll
+                    for (int r = 0; r < D; r++) B[r] = (float)xb[2 * r];
                 } else {
                 const float *xf = (const float *)(x + s0) + (lane >> 5);
 #pragma unroll
@@ -199,7 +206,7 @@ __device__ __forceinline__ void exact_rows_body(const ExactParams &p, const floa
 #pragma unroll
                 for (int r = 0; r < D; r++) {
                     const long long a = s0 + r;
-                    const float2 t = load_sample<S16>(x, a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1));
+                    const float2 t = load_sample<FMT>(x, a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1));
                     B[r] = (a >= 0 && a < p.x_len) ? ((lane >> 5) ? t.y : t.x) : 0.f;
                 }
             }
@@ -319,12 +326,17 @@ __device__ __forceinline__ void exact_rows_body(const ExactParams &p, const floa
 template <int D>
 __global__ __launch_bounds__(kExThreads, exact_full_a(D) ? 3 : 4) void exact_rows_kernel(ExactParams p, const float2 *__restrict__ x)
 {
-    exact_rows_body<D, false>(p, x);
+    exact_rows_body<D, kInF32>(p, x);
 }
 template <int D>
 __global__ __launch_bounds__(kExThreads, exact_full_a(D) ? 3 : 4) void exact_rows_kernel_s16(ExactParams p, const float2 *__restrict__ x)
 {
-    exact_rows_body<D, true>(p, x);
+    exact_rows_body<D, kInS16>(p, x);
+}
+template <int D>
+__global__ __launch_bounds__(kExThreads, exact_full_a(D) ? 3 : 4) void exact_rows_kernel_s8(ExactParams p, const float2 *__restrict__ x)
+{
+    exact_rows_body<D, kInS8>(p, x);
 }
 
 typedef void (*ExactRowsKernel)(ExactParams, const float2 *);
@@ -332,11 +344,11 @@ typedef void (*ExactRowsKernel)(ExactParams, const float2 *);
 // (Round 6 also built a vector-lane form for D <= 4 -- a lane = an output row, its 14 D samples in registers, the taps as scalar
 // operands, no LDS and no barrier per channel -- bit-identical to this kernel on 164 M rows and SLOWER: 2.58 ms against 2.05 for
 // 145 M rows at D = 4 (profiles/r06_t_ubench_exact.txt); removed.)
-template <bool S16 = false>
+template <int FMT = kInF32>
 inline ExactRowsKernel exact_rows_pick(int D)
 {
     switch (D) {
-#define BTGPU_EX(n) case n: if constexpr (S16) return exact_rows_kernel_s16<n>; else return exact_rows_kernel<n>;
+#define BTGPU_EX(n) case n: if constexpr (FMT == kInS8) return exact_rows_kernel_s8<n>; else if constexpr (FMT == kInS16) return exact_rows_kernel_s16<n>; else return exact_rows_kernel<n>;
         BTGPU_EX(2) BTGPU_EX(3) BTGPU_EX(4) BTGPU_EX(5) BTGPU_EX(6) BTGPU_EX(7) BTGPU_EX(8) BTGPU_EX(9) BTGPU_EX(10) BTGPU_EX(11) BTGPU_EX(12) BTGPU_EX(13)
         BTGPU_EX(14) BTGPU_EX(15) BTGPU_EX(16) BTGPU_EX(17) BTGPU_EX(18) BTGPU_EX(19) BTGPU_EX(20) BTGPU_EX(21) BTGPU_EX(22) BTGPU_EX(23) BTGPU_EX(24) BTGPU_EX(25)
         BTGPU_EX(50)

@@ -39,7 +39,9 @@ inline size_t exact_dense_lds_bytes(int D)
     return (size_t)(kExCols * exact_dense_cs(D) + kExCols * kEdDS + kExWaves * 2 * kExDenseRows + 260) * sizeof(float);
 }
 
-template <bool S16>
+// FMT: input format (kernels.hip.h); the staging loads single samples (a tile's first sample has either parity), for int8 as
+// 16-bit loads that a wave issues over 128 consecutive bytes
+template <int FMT>
 __device__ __forceinline__ void exact_dense_body(const ExactParams &p, const float2 *__restrict__ x)
 {
 #pragma clang fp contract(off)
@@ -78,10 +80,10 @@ __device__ __forceinline__ void exact_dense_body(const ExactParams &p, const flo
             const bool inside = sb >= 0 && sb + total <= p.x_len;  // uniform
             for (int s = tid; s < total; s += kExThreads) {
                 float2 v;
-                if (inside) v = load_sample<S16>(x, sb + s);
+                if (inside) v = load_sample<FMT>(x, sb + s);
                 else {
                     const long long a = sb + s;
-                    v = load_sample<S16>(x, a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1));
+                    v = load_sample<FMT>(x, a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1));
                     if (!(a >= 0 && a < p.x_len)) v = make_float2(0.f, 0.f);
                 }
                 Bs[m * CS + r] = v.x;
@@ -191,13 +193,18 @@ __device__ __forceinline__ void exact_dense_body(const ExactParams &p, const flo
 
 __global__ __launch_bounds__(kExThreads, 2) void exact_dense_kernel(ExactParams p, const float2 *__restrict__ x)
 {
-    exact_dense_body<false>(p, x);
+    exact_dense_body<kInF32>(p, x);
 }
 // (a template only so that it can be instantiated in the int16 kernels' translation unit: s16_inst.h)
 template <int V = 0>
 __global__ __launch_bounds__(kExThreads, 2) void exact_dense_kernel_s16(ExactParams p, const float2 *__restrict__ x)
 {
-    exact_dense_body<true>(p, x);
+    exact_dense_body<kInS16>(p, x);
+}
+template <int V = 0>
+__global__ __launch_bounds__(kExThreads, 2) void exact_dense_kernel_s8(ExactParams p, const float2 *__restrict__ x)
+{
+    exact_dense_body<kInS8>(p, x);
 }
 
 }  // namespace btgpu

@@ -67,42 +67,81 @@ constexpr int kVerRows = 1416;    // rows of a window the exact stage's clock re
 constexpr int kVerTile = 127;     // new demodulated rows per tile of verify_ddc_kernel (128 outputs, the first is the demod halo)
 
 // ------------------------------------------------------------------------------------
-// Input formats of the stream x.  Every kernel that reads x has its body templated on S16 (false: x is interleaved float32,
-// 8 bytes per complex sample).  S16 = true: x points at interleaved int16 (re in the low half of a
-// 32-bit word, im in the high half, 4 bytes per sample) and is widened HERE, at the load, with (float)int16 and no scale
-// factor -- int16 -> float32 is exact, so everything behind the load sees the bits the float form would have seen.  The
-// pointer keeps its type (const float2 *) in every parameter block and signature; it is reinterpreted in these helpers only.
+// Input formats of the stream x.  Every kernel that reads x has its body templated on the format FMT:
+//   kInF32: x is interleaved float32, 8 bytes per complex sample.
+//   kInS16: x points at interleaved int16 (re in the low half of a 32-bit word, im in the high half, 4 bytes per sample).
+//   kInS8 : x points at interleaved int8 (re in the low byte of a 16-bit word, im in the high byte, 2 bytes per sample; one
+//           32-bit word holds TWO samples).
+// The integer forms are widened HERE, at the load, with (float)intN and no scale factor -- intN -> float32 is exact, so
+// everything behind the load sees the bits the float form would have seen.  The pointer keeps its type (const float2 *) in
+// every parameter block and signature; it is reinterpreted in these helpers only.
+//
+// int8 widening: sign-extend each byte and convert.  gfx950 does both in ONE instruction per float -- v_cvt_f32_i32 with
+// an SDWA source select (sext(v) src0_sel:BYTE_k), which the compiler forms from (float)(int8_t)(w >> 8k) -- so a sample costs
+// 2 VALU operations, like an int16 sample.  The alternative (flip the sign bits with one XOR, convert the bytes unsigned,
+// subtract 128) compiles to 10 operations per word of two samples, 5 per sample (the compiler moves the subtract into the
+// integer domain and then converts signed anyway); it also leaves a subtract that later arithmetic could absorb.  The
+// sign-extending form has no floating-point operation behind the conversion: nothing for fp-contract(fast) to fuse.
+// (instruction counts: read from the gfx950 disassembly; not timed)
+//
+// int8 alignment: the widest load of an int8 stream is the PAIR, one aligned 32-bit word (samples i, i + 1 with i even), so
+// the stream's base must be 4-byte aligned (btgpu.h).  Kernels that stage pairs start their span at an even sample (interior:
+// whole words; edge tiles: single samples, clamped into [0, x_len)); kernels whose first sample has either parity (odd `first`,
+// odd seg_stride, odd D) load single samples, 2-byte aligned 16-bit loads.  No load touches a byte outside [x, x + 2 x_len).
 // ------------------------------------------------------------------------------------
+enum InFmt : int { kInF32 = 0, kInS16 = 1, kInS8 = 2 };
+// K<ARGS...> or its int16- / int8-input twin K_s16<ARGS...> / K_s8<ARGS...>, by a run-time format
+#define BTGPU_KIN(fmt, K, ...) ((fmt) == ::btgpu::kInS8 ? K##_s8<__VA_ARGS__> : (fmt) == ::btgpu::kInS16 ? K##_s16<__VA_ARGS__> : K<__VA_ARGS__>)
 __device__ __forceinline__ float2 s16_widen(uint32_t w)          // one sample: sign-extend both halves, convert
 {
     return make_float2((float)(int16_t)(w & 0xffffu), (float)((int32_t)w >> 16));
 }
-template <bool S16>
+__device__ __forceinline__ float2 s8_widen(uint32_t h)           // one sample in the low 16 bits: two v_cvt_f32_i32 sext(BYTE_k)
+{
+    return make_float2((float)(int8_t)(h & 0xffu), (float)(int8_t)((h >> 8) & 0xffu));
+}
+__device__ __forceinline__ float4 s8_widen_pair(uint32_t w)      // two samples, one word
+{
+    return make_float4((float)(int8_t)(w & 0xffu), (float)(int8_t)((w >> 8) & 0xffu), (float)(int8_t)((w >> 16) & 0xffu), (float)((int32_t)w >> 24));
+}
+template <int FMT>
 __device__ __forceinline__ float2 load_sample(const float2 *x, long long i)
 {
-    if constexpr (S16) return s16_widen(((const uint32_t *)x)[i]);
+    if constexpr (FMT == kInS16) return s16_widen(((const uint32_t *)x)[i]);
+    else if constexpr (FMT == kInS8) return s8_widen(((const uint16_t *)x)[i]);
     else return x[i];
 }
-// samples i, i + 1 as one load: 16 bytes (float) or 8 bytes (int16); i even and x aligned to that size
-template <bool S16>
+// samples i, i + 1 as one load: 16 bytes (float), 8 bytes (int16) or 4 bytes (int8); i even and x aligned to that size
+template <int FMT>
 __device__ __forceinline__ float4 load_sample_pair(const float2 *x, long long i)
 {
-    if constexpr (S16) {
+    if constexpr (FMT == kInS16) {
         const uint2 w = *(const uint2 *)((const uint32_t *)x + i);
         const float2 a = s16_widen(w.x), b = s16_widen(w.y);
         return make_float4(a.x, a.y, b.x, b.y);
-    } else return *(const float4 *)(x + i);
+    } else if constexpr (FMT == kInS8) return s8_widen_pair(*(const uint32_t *)((const uint16_t *)x + i));
+    else return *(const float4 *)(x + i);
 }
 
-// the same pair held RAW in registers (what the bank kernels prefetch a tile ahead: half the registers with int16) and widened
-// just before the LDS write
-template <bool S16> struct InPiece { typedef float4 type; };
-template <> struct InPiece<true> { typedef uint2 type; };
+// the same pair held RAW in registers (what the bank kernels prefetch a tile ahead: half the registers with int16, a quarter
+// with int8) and widened just before the LDS write
+template <int FMT> struct InPiece { typedef float4 type; };
+template <> struct InPiece<kInS16> { typedef uint2 type; };
+template <> struct InPiece<kInS8> { typedef uint32_t type; };
 __device__ __forceinline__ float4 piece_widen(const float4 &q) { return q; }
 __device__ __forceinline__ float4 piece_widen(const uint2 &w)
 {
     const float2 a = s16_widen(w.x), b = s16_widen(w.y);
     return make_float4(a.x, a.y, b.x, b.y);
+}
+__device__ __forceinline__ float4 piece_widen(const uint32_t &w) { return s8_widen_pair(w); }
+// byte address of sample i of the stream
+template <int FMT>
+__device__ __forceinline__ const char *sample_addr(const float2 *x, long long i)
+{
+    if constexpr (FMT == kInS16) return (const char *)((const uint32_t *)x + i);
+    else if constexpr (FMT == kInS8) return (const char *)((const uint16_t *)x + i);
+    else return (const char *)(x + i);
 }
 
 // ------------------------------------------------------------------------------------
@@ -116,9 +155,10 @@ __device__ __forceinline__ float4 piece_widen(const uint2 &w)
 // workgroup's tile is staged through LDS once per tap chunk and shared by the CPB
 // channels; taps are wave-uniform (scalar loads).
 // ------------------------------------------------------------------------------------
-// (The kernels proper are thin: X_kernel<...> is the float-input form under its old name, X_kernel_s16<...> the int16-input form of
-// the same body -- a trailing template parameter would have renamed every existing kernel.)
-template <int CPB, bool S16>
+// (The kernels proper are thin: X_kernel<...> is the float-input form under its old name, X_kernel_s16<...> / X_kernel_s8<...> the
+// int16- and int8-input forms of the same body -- a trailing template parameter would have renamed every existing kernel.)
+// int8: the tile's first sample has either parity, so the staging loads single samples (16-bit loads, clamped like the others).
+template <int CPB, int FMT>
 __device__ __forceinline__ void ddc_direct_body(
     const float2 *__restrict__ x, long long x_len, long long first, int D, int ntp, int JC,
     const float2 *__restrict__ taps, const float2 *__restrict__ rot, int Q,
@@ -164,7 +204,7 @@ __device__ __forceinline__ void ddc_direct_body(
             for (int k = 0; k < 4; k++) {
                 const long long a = base + s0 + k * T;
                 const long long ac = a < 0 ? 0 : (a < x_len ? a : x_len - 1);
-                v[k] = load_sample<S16>(x, ac);
+                v[k] = load_sample<FMT>(x, ac);
             }
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -226,9 +266,11 @@ __device__ __forceinline__ void ddc_direct_body(
     int seg_len, long long seg_stride
 #define BTGPU_DDC_ARGS x, x_len, first, D, ntp, JC, taps, rot, Q, rot_step_turns, Y, G, ystride, nch, seg_len, seg_stride
 template <int CPB>
-__global__ __launch_bounds__(256) void ddc_direct_kernel(BTGPU_DDC_PARAMS) { ddc_direct_body<CPB, false>(BTGPU_DDC_ARGS); }
+__global__ __launch_bounds__(256) void ddc_direct_kernel(BTGPU_DDC_PARAMS) { ddc_direct_body<CPB, kInF32>(BTGPU_DDC_ARGS); }
 template <int CPB>
-__global__ __launch_bounds__(256) void ddc_direct_kernel_s16(BTGPU_DDC_PARAMS) { ddc_direct_body<CPB, true>(BTGPU_DDC_ARGS); }
+__global__ __launch_bounds__(256) void ddc_direct_kernel_s16(BTGPU_DDC_PARAMS) { ddc_direct_body<CPB, kInS16>(BTGPU_DDC_ARGS); }
+template <int CPB>
+__global__ __launch_bounds__(256) void ddc_direct_kernel_s8(BTGPU_DDC_PARAMS) { ddc_direct_body<CPB, kInS8>(BTGPU_DDC_ARGS); }
 #undef BTGPU_DDC_PARAMS
 #undef BTGPU_DDC_ARGS
 

@@ -234,8 +234,9 @@ __device__ __forceinline__ int xcd_remap(int b, int n)
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-// S16: int16 input stream (kernels.hip.h), widened between the loads and the LDS write of the staging
-template <int Q, int S, int NT, bool REAL, bool CHAN, int NTH, bool FUSEN, bool S16>
+// FMT: input format of the stream (kernels.hip.h); int16 / int8 are widened between the loads and the LDS write of the staging
+// (int8: a piece is one aligned 32-bit word -- the span starts at an even sample; edge tiles load single samples, clamped)
+template <int Q, int S, int NT, bool REAL, bool CHAN, int NTH, bool FUSEN, int FMT>
 __device__ __forceinline__ void pfb100_body(const PfbParams &p)
 {
     constexpr int DH = S * 50;                               // hop: 2 D = S * 100
@@ -298,7 +299,7 @@ __device__ __forceinline__ void pfb100_body(const PfbParams &p)
         const long long a = a0 + 2 * (long long)i;
         const long long ac = a < 0 ? 0 : (a + 1 < p.x_len ? a : (p.x_len >= 2 ? p.x_len - 2 : 0));
         const long long bc = ac + 1 < p.x_len ? ac + 1 : ac;
-        const float2 q0 = load_sample<S16>(p.x, ac), q1 = load_sample<S16>(p.x, bc);
+        const float2 q0 = load_sample<FMT>(p.x, ac), q1 = load_sample<FMT>(p.x, bc);
         float4 v;
         // sample a is q0 when a was in range, sample a + 1 is q1 (or q0 when a was clamped up by one)
         const bool in0 = a >= 0 && a < p.x_len, in1 = a + 1 >= 0 && a + 1 < p.x_len;
@@ -350,7 +351,7 @@ __device__ __forceinline__ void pfb100_body(const PfbParams &p)
             for (int j = 0; j < PER; j++) v[j] = make_float4(1.f, 0.5f, -0.25f, 0.125f);
         } else if (interior) {                               // block-uniform: one straight run of loads
 #pragma unroll
-            for (int j = 0; j < PER; j++) v[j] = load_sample_pair<S16>(p.x, a0 + 2 * (l + j * NTH < N4 ? l + j * NTH : N4 - 1));
+            for (int j = 0; j < PER; j++) v[j] = load_sample_pair<FMT>(p.x, a0 + 2 * (l + j * NTH < N4 ? l + j * NTH : N4 - 1));
         } else {
 #pragma unroll
             for (int j = 0; j < PER; j++) v[j] = load_piece_edge(a0, l + j * NTH < N4 ? l + j * NTH : N4 - 1);
@@ -670,12 +671,17 @@ __device__ __forceinline__ void pfb100_body(const PfbParams &p)
 template <int Q, int S, int NT, bool REAL, bool CHAN, int NTH, bool FUSEN = false>
 __global__ __launch_bounds__(NTH, (FUSEN ? 3 * NTH / 256 : 1)) void pfb100_kernel(PfbParams p)
 {
-    pfb100_body<Q, S, NT, REAL, CHAN, NTH, FUSEN, false>(p);
+    pfb100_body<Q, S, NT, REAL, CHAN, NTH, FUSEN, kInF32>(p);
 }
 template <int Q, int S, int NT, bool REAL, bool CHAN, int NTH, bool FUSEN = false>
 __global__ __launch_bounds__(NTH, (FUSEN ? 3 * NTH / 256 : 1)) void pfb100_kernel_s16(PfbParams p)
 {
-    pfb100_body<Q, S, NT, REAL, CHAN, NTH, FUSEN, true>(p);
+    pfb100_body<Q, S, NT, REAL, CHAN, NTH, FUSEN, kInS16>(p);
+}
+template <int Q, int S, int NT, bool REAL, bool CHAN, int NTH, bool FUSEN = false>
+__global__ __launch_bounds__(NTH, (FUSEN ? 3 * NTH / 256 : 1)) void pfb100_kernel_s8(PfbParams p)
+{
+    pfb100_body<Q, S, NT, REAL, CHAN, NTH, FUSEN, kInS8>(p);
 }
 
 // tile sums -> per-slot-block sums P[c][b] and block-head sums Pt[c][b] (first `tail` instants of

@@ -149,7 +149,9 @@ __device__ __forceinline__ void setprio_dyn(int v)
 // S16: the input stream is interleaved int16 (kernels.hip.h): a lane's prefetched piece is 8 bytes instead of 16 for the same two
 // samples, kept raw in (half as many) registers across the tile and widened at the LDS write; the edge tiles widen sample by
 // sample.  LDS layout and everything behind the staging are the float form's.
-template <int NTH, bool REAL, int KT, int OPT, bool S16>
+// int8: the piece is ONE 32-bit word (the span starts at an even sample, so every piece is an aligned word of a 4-byte
+// aligned stream): at most six raw registers per lane carry the next tile instead of twenty-four.
+template <int NTH, bool REAL, int KT, int OPT, int FMT>
 __device__ __forceinline__ void pfb100f_body(const PfbParams &p)
 {
     static_assert(NTH == 256 || NTH == 320 || NTH == 512, "lane roles are laid out for four, five or eight waves");
@@ -246,15 +248,16 @@ __device__ __forceinline__ void pfb100f_body(const PfbParams &p)
     // are staged in place when their turn comes, element by element with clamped addresses (zeros outside).
     // (named registers, not an array: an array that lives across the tile loop stays in scratch memory)
     static_assert(PER <= 6, "explicit prefetch registers below");
-    typedef typename InPiece<S16>::type PV;                      // two samples as they lie in the stream: 16 bytes, or 8 (int16)
+    typedef typename InPiece<FMT>::type PV;                      // two samples as they lie in the stream: 16 bytes, 8 (int16) or 4 (int8)
     constexpr unsigned PB = (unsigned)sizeof(PV);
     PV v0, v1, v2, v3, v4, v5;
-    if constexpr (S16) v0 = v1 = v2 = v3 = v4 = v5 = PV{};
+    if constexpr (FMT != kInF32) v0 = v1 = v2 = v3 = v4 = v5 = PV{};
     else v0 = v1 = v2 = v3 = v4 = v5 = make_float4(0.f, 0.f, 0.f, 0.f);
     auto load_span = [&](int tile, int l) {
         // uniform base + 32-bit lane offset (scalar base registers, no 64-bit lane arithmetic); only the last piece clamps
         // (span_start is even: every piece is a naturally aligned load as long as the stream's base is aligned to a piece)
-        const char *xb = S16 ? (const char *)((const uint32_t *)p.x + span_start(tile)) : (const char *)(p.x + span_start(tile));
+        const char *xb = FMT == kInS8 ? sample_addr<kInS8>(p.x, span_start(tile))
+                         : FMT == kInS16 ? (const char *)((const uint32_t *)p.x + span_start(tile)) : (const char *)(p.x + span_start(tile));
         const unsigned o = (unsigned)l * PB;
         auto at = [&](int j) {
             const unsigned oj = (j + 1) * NTH <= N4 ? o : (unsigned)(l + j * NTH < N4 ? l : N4 - 1 - j * NTH) * PB;
@@ -269,7 +272,7 @@ __device__ __forceinline__ void pfb100f_body(const PfbParams &p)
         for (int i = l; i < N4; i += NTH) {
             const long long s0 = a0 + 2LL * i, s1 = s0 + 1;
             const bool in0 = s0 >= 0 && s0 < p.x_len, in1 = s1 >= 0 && s1 < p.x_len;
-            const float2 q0 = load_sample<S16>(p.x, in0 ? s0 : 0), q1 = load_sample<S16>(p.x, in1 ? s1 : 0);
+            const float2 q0 = load_sample<FMT>(p.x, in0 ? s0 : 0), q1 = load_sample<FMT>(p.x, in1 ? s1 : 0);
             ((float4 *)xs)[i] = make_float4(in0 ? q0.x : 0.f, in0 ? q0.y : 0.f, in1 ? q1.x : 0.f, in1 ? q1.y : 0.f);
         }
     };
@@ -634,12 +637,17 @@ __device__ __forceinline__ void pfb100f_body(const PfbParams &p)
 template <int NTH, bool REAL, int KT, int OPT = 0>
 __global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 320 ? 4 : 3)) void pfb100f_kernel(PfbParams p)   // (HIP: the second number is waves per SIMD)
 {
-    pfb100f_body<NTH, REAL, KT, OPT, false>(p);
+    pfb100f_body<NTH, REAL, KT, OPT, kInF32>(p);
 }
 template <int NTH, bool REAL, int KT, int OPT = 0>
 __global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 320 ? 4 : 3)) void pfb100f_kernel_s16(PfbParams p)
 {
-    pfb100f_body<NTH, REAL, KT, OPT, true>(p);
+    pfb100f_body<NTH, REAL, KT, OPT, kInS16>(p);
+}
+template <int NTH, bool REAL, int KT, int OPT = 0>
+__global__ __launch_bounds__(NTH, NTH == 512 ? ((OPT & 512) ? 4 : 6) : (NTH == 320 ? 4 : 3)) void pfb100f_kernel_s8(PfbParams p)
+{
+    pfb100f_body<NTH, REAL, KT, OPT, kInS8>(p);
 }
 
 }  // namespace btgpu

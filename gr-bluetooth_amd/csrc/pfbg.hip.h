@@ -65,7 +65,9 @@ struct PfbgParams {
     int run;                     // new instants per workgroup (channel bank: a multiple of TT)
 };
 
-template <bool REAL, bool CHAN, bool S16>
+// FMT: input format of the stream (kernels.hip.h); int8 pieces are aligned 32-bit words from the even sample a0, edge chunks
+// load single samples
+template <bool REAL, bool CHAN, int FMT>
 __device__ __forceinline__ void pfbg_body(const PfbgParams &pp)
 {
 #pragma clang fp contract(fast)
@@ -116,11 +118,11 @@ __device__ __forceinline__ void pfbg_body(const PfbgParams &pp)
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const int i = i0 + l + j * NTH < N4 ? i0 + l + j * NTH : N4 - 1;
-                    if (interior) { if constexpr (S16) v[j] = load_sample_pair<true>(p.x, a0 + 2LL * i); else v[j] = ((const float4 *)(p.x + a0))[i]; }
+                    if (interior) { if constexpr (FMT != kInF32) v[j] = load_sample_pair<FMT>(p.x, a0 + 2LL * i); else v[j] = ((const float4 *)(p.x + a0))[i]; }
                     else {
                         const long long s0 = a0 + 2LL * i, s1 = s0 + 1;
                         const bool in0 = s0 >= 0 && s0 < p.x_len, in1 = s1 >= 0 && s1 < p.x_len;
-                        const float2 q0 = load_sample<S16>(p.x, in0 ? s0 : 0), q1 = load_sample<S16>(p.x, in1 ? s1 : 0);
+                        const float2 q0 = load_sample<FMT>(p.x, in0 ? s0 : 0), q1 = load_sample<FMT>(p.x, in1 ? s1 : 0);
                         v[j] = make_float4(in0 ? q0.x : 0.f, in0 ? q0.y : 0.f, in1 ? q1.x : 0.f, in1 ? q1.y : 0.f);
                     }
                 }
@@ -224,19 +226,24 @@ __device__ __forceinline__ void pfbg_body(const PfbgParams &pp)
 template <bool REAL, bool CHAN>
 __global__ __launch_bounds__(kPfbgThreads) void pfbg_kernel(PfbgParams p)
 {
-    pfbg_body<REAL, CHAN, false>(p);
+    pfbg_body<REAL, CHAN, kInF32>(p);
 }
 template <bool REAL, bool CHAN>
 __global__ __launch_bounds__(kPfbgThreads) void pfbg_kernel_s16(PfbgParams p)
 {
-    pfbg_body<REAL, CHAN, true>(p);
+    pfbg_body<REAL, CHAN, kInS16>(p);
+}
+template <bool REAL, bool CHAN>
+__global__ __launch_bounds__(kPfbgThreads) void pfbg_kernel_s8(PfbgParams p)
+{
+    pfbg_body<REAL, CHAN, kInS8>(p);
 }
 
 // ---- launches.  L(kernel, grid, threads, lds_bytes, params) performs one; B is bank_launch.h's BankBuffers, arows the bank's
 // pack_dft_rows on the device.  (Kept here: bank_launch.h is also compiled for the host emulator, which has no wave shuffles.)
 template <class Launcher, class B>
 inline int launch_channel_bank_g(const Design &des, const FastPath &fp, const B &b, const float4 *arows, size_t x_len,
-                                 long long w0, long long G, Launcher &&L, bool s16 = false)
+                                 long long w0, long long G, Launcher &&L, int fmt = 0)
 {
     const btgpu_design &d = des.d;
     const PfbBank &bk = fp.channel;
@@ -257,14 +264,14 @@ inline int launch_channel_bank_g(const Design &des, const FastPath &fp, const B 
     g.run = kt * p.TT;
     const size_t lds = pfbg_lds_bytes(bk.M, bk.D, bk.Q, true, bk.real_taps);
     const int grid = (p.ntiles + kt - 1) / kt;
-    if (bk.real_taps) L(s16 ? pfbg_kernel_s16<true, true> : pfbg_kernel<true, true>, grid, kPfbgThreads, lds, g);
-    else L(s16 ? pfbg_kernel_s16<false, true> : pfbg_kernel<false, true>, grid, kPfbgThreads, lds, g);
+    if (bk.real_taps) L(BTGPU_KIN(fmt, pfbg_kernel, true, true), grid, kPfbgThreads, lds, g);
+    else L(BTGPU_KIN(fmt, pfbg_kernel, false, true), grid, kPfbgThreads, lds, g);
     return p.ntiles;
 }
 
 template <class Launcher, class B>
 inline void launch_noise_bank_g(const Design &des, const FastPath &fp, const B &b, const float4 *arows, size_t x_len,
-                                long long w0, int S, Launcher &&L, bool s16 = false)
+                                long long w0, int S, Launcher &&L, int fmt = 0)
 {
     const btgpu_design &d = des.d;
     const NoiseStage &ns = fp.noise;
@@ -281,7 +288,7 @@ inline void launch_noise_bank_g(const Design &des, const FastPath &fp, const B &
     p.Z = b.Z; p.zstride = b.zstride;
     g.arows = arows; g.ng = pfbg_groups(bk.M);
     g.run = kPfbgNoiseRun;
-    L(s16 ? pfbg_kernel_s16<false, false> : pfbg_kernel<false, false>, (int)((p.T + g.run - 1) / g.run), kPfbgThreads,
+    L(BTGPU_KIN(fmt, pfbg_kernel, false, false), (int)((p.T + g.run - 1) / g.run), kPfbgThreads,
       pfbg_lds_bytes(bk.M, bk.D, bk.Q, false, false), g);
 }
 

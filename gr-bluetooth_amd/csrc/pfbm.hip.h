@@ -99,8 +99,9 @@ __device__ __forceinline__ void fft8(cf (&u)[8])
 // FN (with F8, CHAN): squelch stage 1 (the 8-bin noise bank, 15 taps per branch, hop n_D) computed from the same staged input --
 // a launch, a second read of the input and 0.42 ms of a 2 ms step at C8 (pfbm_kernel<false, false, 8, 15, true> stays the
 // stand-alone form).
-// S16: int16 input stream (kernels.hip.h), widened between the loads and the LDS write of the staging
-template <bool REAL, bool CHAN, int MC, int QC, bool F8, bool FN, bool S16>
+// FMT: input format of the stream (kernels.hip.h); int16 / int8 are widened between the loads and the LDS write of the staging
+// (int8: interior pieces are aligned 32-bit words from the even sample a0; edge tiles load single samples, clamped)
+template <bool REAL, bool CHAN, int MC, int QC, bool F8, bool FN, int FMT>
 __device__ __forceinline__ void pfbm_body(const PfbmParams &p)
 {
     static_assert(!F8 || MC == 8, "the FFT variant is the 8-bin bank");
@@ -134,12 +135,12 @@ __device__ __forceinline__ void pfbm_body(const PfbmParams &p)
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int i = i0 + l + j * NTH < N4 ? i0 + l + j * NTH : N4 - 1;
-                if (interior) { if constexpr (S16) v[j] = load_sample_pair<true>(p.x, a0 + 2LL * i); else v[j] = ((const float4 *)(p.x + a0))[i]; }
+                if (interior) { if constexpr (FMT != kInF32) v[j] = load_sample_pair<FMT>(p.x, a0 + 2LL * i); else v[j] = ((const float4 *)(p.x + a0))[i]; }
                 else {
                     const long long a = a0 + 2LL * i;
                     const long long ac = a < 0 ? 0 : (a < p.x_len ? a : p.x_len - 1);
                     const long long bc = a + 1 < 0 ? 0 : (a + 1 < p.x_len ? a + 1 : p.x_len - 1);
-                    const float2 q0 = load_sample<S16>(p.x, ac), q1 = load_sample<S16>(p.x, bc);
+                    const float2 q0 = load_sample<FMT>(p.x, ac), q1 = load_sample<FMT>(p.x, bc);
                     const bool in0 = a >= 0 && a < p.x_len, in1 = a + 1 >= 0 && a + 1 < p.x_len;
                     v[j] = make_float4(in0 ? q0.x : 0.f, in0 ? q0.y : 0.f, in1 ? q1.x : 0.f, in1 ? q1.y : 0.f);
                 }
@@ -406,12 +407,17 @@ __device__ __forceinline__ void pfbm_body(const PfbmParams &p)
 template <bool REAL, bool CHAN, int MC = 0, int QC = 0, bool F8 = false, bool FN = false>
 __global__ __launch_bounds__(kPfbmThreads) void pfbm_kernel(PfbmParams p)
 {
-    pfbm_body<REAL, CHAN, MC, QC, F8, FN, false>(p);
+    pfbm_body<REAL, CHAN, MC, QC, F8, FN, kInF32>(p);
 }
 template <bool REAL, bool CHAN, int MC = 0, int QC = 0, bool F8 = false, bool FN = false>
 __global__ __launch_bounds__(kPfbmThreads) void pfbm_kernel_s16(PfbmParams p)
 {
-    pfbm_body<REAL, CHAN, MC, QC, F8, FN, true>(p);
+    pfbm_body<REAL, CHAN, MC, QC, F8, FN, kInS16>(p);
+}
+template <bool REAL, bool CHAN, int MC = 0, int QC = 0, bool F8 = false, bool FN = false>
+__global__ __launch_bounds__(kPfbmThreads) void pfbm_kernel_s8(PfbmParams p)
+{
+    pfbm_body<REAL, CHAN, MC, QC, F8, FN, kInS8>(p);
 }
 
 }  // namespace btgpu

@@ -70,7 +70,8 @@ int multi_block::run_work(int noutput_items, gr_vector_const_void_star &input_it
 {
     size_t consumed = 0;
     const size_t n_items = (size_t)(history() - 1) + (size_t)noutput_items;
-    int rc = d_input_shorts ? btgpu_work_s16(d_gpu, (const int16_t *)input_items[0], n_items, &consumed)
+    int rc = d_input_bytes ? btgpu_work_s8(d_gpu, (const int8_t *)input_items[0], n_items, &consumed)
+           : d_input_shorts ? btgpu_work_s16(d_gpu, (const int16_t *)input_items[0], n_items, &consumed)
                             : btgpu_work(d_gpu, (const float *)input_items[0], n_items, &consumed);
     if (rc == BTGPU_EOVERFLOW)                        // records were dropped: the reference would have printed them
         fprintf(stderr, "Warning: hit buffer overflow, detections of this call were dropped (%s)\n", btgpu_last_error(d_gpu));
@@ -127,13 +128,17 @@ void multi_block::drain(btgpu_handle *g)
 
 long multi_block::run_partitioned(const gr_complex *items, size_t n_new, int ngpus, bool all_on_device0)
 {
-    return run_partitioned_any(items, false, n_new, ngpus, all_on_device0);
+    return run_partitioned_any(items, (int)sizeof(gr_complex), n_new, ngpus, all_on_device0);
 }
 long multi_block::run_partitioned(const int16_t *items, size_t n_new, int ngpus, bool all_on_device0)
 {
-    return run_partitioned_any(items, true, n_new, ngpus, all_on_device0);
+    return run_partitioned_any(items, 4, n_new, ngpus, all_on_device0);
 }
-long multi_block::run_partitioned_any(const void *items, bool shorts, size_t n_new, int ngpus, bool all_on_device0)
+long multi_block::run_partitioned(const int8_t *items, size_t n_new, int ngpus, bool all_on_device0)
+{
+    return run_partitioned_any(items, 2, n_new, ngpus, all_on_device0);
+}
+long multi_block::run_partitioned_any(const void *items, int item_bytes, size_t n_new, int ngpus, bool all_on_device0)
 {
     const size_t H = (size_t)d_design.history, slot = (size_t)d_design.samples_per_slot, mg = (size_t)d_design.left_margin;
     const uint64_t total = n_new / slot;
@@ -161,7 +166,7 @@ long multi_block::run_partitioned_any(const void *items, bool shorts, size_t n_n
     std::vector<int> rcs((size_t)ngpus, BTGPU_OK);
     std::vector<std::thread> th;
     const char *base = (const char *)items;                            // items[0] = absolute sample first_abs*slot - (H-1)
-    const size_t isz = shorts ? 2 * sizeof(int16_t) : sizeof(gr_complex);   // bytes per item
+    const size_t isz = (size_t)item_bytes;                             // bytes per item
     for (int r = 0; r < ngpus; r++) {
         const uint64_t b = total / (uint64_t)ngpus, rem = total % (uint64_t)ngpus;
         const uint64_t first = (uint64_t)r * b + std::min<uint64_t>((uint64_t)r, rem), cnt = b + ((uint64_t)r < rem ? 1 : 0);
@@ -172,8 +177,9 @@ long multi_block::run_partitioned_any(const void *items, bool shorts, size_t n_n
             const size_t have = std::min(mg, w0);                      // the stream start has zeros there (implied)
             const void *seg = base + (w0 - have) * isz;
             const size_t n_seg = have + H + (size_t)(cnt - 1) * slot;
-            int rc = shorts ? btgpu_process_host_s16(g[(size_t)r], (const int16_t *)seg, n_seg, have, first_abs + first, cnt)
-                            : btgpu_process_host(g[(size_t)r], (const float *)seg, n_seg, have, first_abs + first, cnt);
+            int rc = isz == 2 ? btgpu_process_host_s8(g[(size_t)r], (const int8_t *)seg, n_seg, have, first_abs + first, cnt)
+                   : isz == 4 ? btgpu_process_host_s16(g[(size_t)r], (const int16_t *)seg, n_seg, have, first_abs + first, cnt)
+                              : btgpu_process_host(g[(size_t)r], (const float *)seg, n_seg, have, first_abs + first, cnt);
             if (rc == BTGPU_OK || rc == BTGPU_EOVERFLOW) { int rf = btgpu_flush(g[(size_t)r]); if (rf != BTGPU_OK) rc = rf; }
             rcs[(size_t)r] = rc;
         });

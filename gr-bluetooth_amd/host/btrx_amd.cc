@@ -1,7 +1,8 @@
 // btrx_amd -- command-line driver, counterpart of the reference's apps/btrx for the two hot-path
 // blocks.  Same flag meanings (apps/btrx:22-60): -f centre frequency (default 2.476e9), -r sample
 // rate (required, >= 2e6), -i input file ('-' = stdin), -s input is interleaved int16 (handed to the block as it is:
-// multi_block::set_input_shorts, widened on the GPU without scaling like interleaved_short_to_complex), -N sample
+// multi_block::set_input_shorts, widened on the GPU without scaling like interleaved_short_to_complex), --s8 input is
+// interleaved int8 (no counterpart in apps/btrx, whose -s means shorts: multi_block::set_input_bytes), -N sample
 // limit, -S all-piconet sniffer (default: LAP sniffer), -t SNR squelch (default 10.0),
 // -w Wireshark TAP sink.  The little scheduler below stands in for GNU Radio's: history()-1 zeros first,
 // work() called with a multiple of output_multiple() new items.  --gpus N (no counterpart in apps/btrx)
@@ -34,13 +35,14 @@ static double eng(const char *s)
 
 static void usage()
 {
-    fprintf(stderr, "usage: btrx_amd -r RATE [-f FREQ] [-i FILE|-] [-s] [-N NSAMPLES] [-S] [-l LAP -p [--aliased]] [-t SNR] [-w] [-c CHUNK_SLOTS] [--gpus N [--all-on-device0]]\n");
+    fprintf(stderr, "usage: btrx_amd -r RATE [-f FREQ] [-i FILE|-] [-s | --s8] [-N NSAMPLES] [-S] [-l LAP -p [--aliased]] [-t SNR] [-w] [-c CHUNK_SLOTS] [--gpus N [--all-on-device0]]\n");
+    fprintf(stderr, "  -s    input is interleaved int16 I/Q;  --s8  input is interleaved int8 I/Q (both unscaled; default: float32)\n");
 }
 
 int main(int argc, char **argv)
 {
     double freq = 2.476e9, rate = 0, snr = 10.0, nsamples = -1;
-    bool sniff = false, shorts = false, tun = false, hop = false, aliased = false;
+    bool sniff = false, shorts = false, bytes = false, tun = false, hop = false, aliased = false;
     long lap = -1;
     std::string file;
     int chunk_slots = 64, gpus = 1;
@@ -61,10 +63,12 @@ int main(int argc, char **argv)
         else if (a == "-p" || a == "--hop") hop = true;                                // apps/btrx:46-47
         else if (a == "--aliased") aliased = true;
         else if (a == "-s" || a == "--input-shorts") shorts = true;
+        else if (a == "--s8" || a == "--input-bytes") bytes = true;
         else if (a == "-w" || a == "--wireshark") tun = true;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); usage(); return 1; }
     }
+    if (shorts && bytes) { fprintf(stderr, "-s and --s8 exclude each other\n"); return 1; }
     if (rate <= 0) { fprintf(stderr, "Sample rate must be provided\n"); return 1; }             // apps/btrx:70-71
     if (rate < 2e6) { fprintf(stderr, "Sample rate (%d) below minimum (%d)\n", (int)rate, 2000000); return 1; }
     if (file.empty()) { fprintf(stderr, "btrx_amd reads captures only: give -i FILE (or -i -)\n"); return 1; }
@@ -82,15 +86,18 @@ int main(int argc, char **argv)
         return 2;
     }
     const size_t H = blk->history(), mult = (size_t)blk->output_multiple();
-    std::vector<gr_complex> buf(shorts ? 0 : H - 1, gr_complex(0, 0));   // GNU Radio pre-fills history()-1 zeros
+    std::vector<gr_complex> buf(shorts || bytes ? 0 : H - 1, gr_complex(0, 0));   // GNU Radio pre-fills history()-1 zeros
     std::vector<int16_t> sbuf(shorts ? 2 * (H - 1) : 0, 0);        // -s: the items stay int16 (I, Q interleaved), the same zeros in front
+    std::vector<int8_t> bbuf(bytes ? 2 * (H - 1) : 0, 0);          // --s8: the items stay int8
     if (shorts) blk->set_input_shorts();
-    // items held / appended, in either format
-    auto held = [&]() { return shorts ? sbuf.size() / 2 : buf.size(); };
+    if (bytes) blk->set_input_bytes();
+    // items held / appended, in any format
+    auto held = [&]() { return bytes ? bbuf.size() / 2 : shorts ? sbuf.size() / 2 : buf.size(); };
     auto read_items = [&](size_t want) {
         const size_t old = held();
         size_t got;
-        if (shorts) { sbuf.resize(2 * (old + want)); got = fread(&sbuf[2 * old], 2 * sizeof(int16_t), want, fp); sbuf.resize(2 * (old + got)); }
+        if (bytes) { bbuf.resize(2 * (old + want)); got = fread(&bbuf[2 * old], 2, want, fp); bbuf.resize(2 * (old + got)); }
+        else if (shorts) { sbuf.resize(2 * (old + want)); got = fread(&sbuf[2 * old], 2 * sizeof(int16_t), want, fp); sbuf.resize(2 * (old + got)); }
         else { buf.resize(old + want); got = fread(&buf[old], sizeof(gr_complex), want, fp); buf.resize(old + got); }
         return got;
     };
@@ -104,7 +111,8 @@ int main(int argc, char **argv)
         }
         if (fp != stdin) fclose(fp);
         try {
-            if (shorts) blk->run_partitioned(sbuf.data(), held() - (H - 1), gpus, all_on_device0);
+            if (bytes) blk->run_partitioned(bbuf.data(), held() - (H - 1), gpus, all_on_device0);
+            else if (shorts) blk->run_partitioned(sbuf.data(), held() - (H - 1), gpus, all_on_device0);
             else blk->run_partitioned(buf.data(), held() - (H - 1), gpus, all_on_device0);
         } catch (const std::exception &e) {
             fprintf(stderr, "%s\n", e.what());
@@ -125,10 +133,11 @@ int main(int argc, char **argv)
         size_t avail = held() - (H - 1);
         size_t n = avail / mult * mult;
         if (n == 0) continue;
-        gr_vector_const_void_star in(1, shorts ? (const void *)sbuf.data() : (const void *)buf.data());
+        gr_vector_const_void_star in(1, bytes ? (const void *)bbuf.data() : shorts ? (const void *)sbuf.data() : (const void *)buf.data());
         gr_vector_void_star out;
         int consumed = blk->work((int)n, in, out);
-        if (shorts) sbuf.erase(sbuf.begin(), sbuf.begin() + 2 * (size_t)consumed);
+        if (bytes) bbuf.erase(bbuf.begin(), bbuf.begin() + 2 * (size_t)consumed);
+        else if (shorts) sbuf.erase(sbuf.begin(), sbuf.begin() + 2 * (size_t)consumed);
         else buf.erase(buf.begin(), buf.begin() + consumed);
     }
     if (fp != stdin) fclose(fp);

@@ -44,7 +44,9 @@ protected:
     btgpu_config d_cfg{};                 // what d_gpu was created with (run_partitioned clones it per device)
     int d_device = 0;                     // HIP ordinal d_gpu lives on
     bool d_input_shorts = false;          // work()'s items are complex int16 (set_input_shorts)
-    long run_partitioned_any(const void *items, bool shorts, size_t n_new, int ngpus, bool all_on_device0);
+    bool d_input_bytes = false;           // work()'s items are complex int8 (set_input_bytes)
+    // item_bytes: 8 (gr_complex), 4 (complex int16) or 2 (complex int8)
+    long run_partitioned_any(const void *items, int item_bytes, size_t n_new, int ngpus, bool all_on_device0);
 
 public:
     // Time-partitioned run over `ngpus` devices of this node (no GNU Radio counterpart: a flowgraph hands a
@@ -57,11 +59,16 @@ public:
     long run_partitioned(const gr_complex *items, size_t n_new, int ngpus, bool all_on_device0 = false);
     // ... the same for a capture of complex int16 items (interleaved I, Q), which go to the devices as they are
     long run_partitioned(const int16_t *items, size_t n_new, int ngpus, bool all_on_device0 = false);
+    // ... and of complex int8 items (interleaved I, Q: the 8-bit wire formats)
+    long run_partitioned(const int8_t *items, size_t n_new, int ngpus, bool all_on_device0 = false);
     // Declare, before the first work(), that input_items[0] holds complex int16 items (interleaved I, Q: what the
     // reference's flowgraph feeds interleaved_short_to_complex) instead of gr_complex: work() then hands them to
     // btgpu_work_s16 unconverted and unscaled -- half the bytes to the device, the same records.  (In a GNU Radio
     // flowgraph the block's input signature is then a vector of two shorts per item.)
-    void set_input_shorts(bool on = true) { d_input_shorts = on; }
+    void set_input_shorts(bool on = true) { d_input_shorts = on; if (on) d_input_bytes = false; }
+    // The same for complex int8 items (interleaved I, Q, 2 bytes per item: USRP sc8, bladeRF's 8-bit mode, HackRF): work() hands
+    // them to btgpu_work_s8 unconverted and unscaled -- a quarter of the bytes to the device, the same records.
+    void set_input_bytes(bool on = true) { d_input_bytes = on; if (on) d_input_shorts = false; }
     double samples_per_slot() const { return d_design.samples_per_slot; }
     int low_channel() const { return d_design.low_channel; }
     int high_channel() const { return d_design.high_channel; }

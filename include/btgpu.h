@@ -259,6 +259,23 @@ int btgpu_process_host_s16(btgpu_handle *h, const int16_t *iq, size_t n_complex,
 int btgpu_process_device_s16(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
                              uint64_t first_slot, uint64_t n_slots, void *hip_stream);
 
+/* ---- complex int8 input (the 8-bit wire formats: USRP sc8, bladeRF 2.0's 8-bit mode, HackRF) ----
+ * The same three entries for interleaved int8 I/Q, argument for argument: re in the low byte, im in the next, one complex
+ * sample = 2 bytes; sizes, margins and slots stay in COMPLEX samples.  The samples travel to the device as they are -- a
+ * quarter of the float entries' bytes -- and are widened inside the kernels at their input loads with (float)int8, NO scale
+ * factor and no DC correction: exact, so records, demodulated stream and window energies are bit for bit the float entry's
+ * for the same values.  Every configuration btgpu_create accepts takes this format, and a handle may be fed float, int16 or
+ * int8 from call to call (the margin btgpu_work carries stays float32; an int8 call that follows a wider one rounds those few
+ * samples to int8, saturating at -128 / 127).
+ * Alignment: the widest load the kernels issue on an int8 stream is one aligned 32-bit word (two samples), so the device
+ * pointer given to btgpu_process_device_s8 must be 4-byte aligned (BTGPU_EINVAL otherwise); host pointers need 1 byte (they
+ * are staged into buffers of the library's own).  btgpu_push stays float-only. */
+int btgpu_work_s8(btgpu_handle *h, const int8_t *items, size_t n_items, size_t *consumed);
+int btgpu_process_host_s8(btgpu_handle *h, const int8_t *iq, size_t n_complex, size_t left_margin,
+                          uint64_t first_slot, uint64_t n_slots);
+int btgpu_process_device_s8(btgpu_handle *h, const void *d_iq, size_t n_complex, size_t left_margin,
+                            uint64_t first_slot, uint64_t n_slots, void *hip_stream);
+
 /* Drain queued hits, ordered by (slot, channel, kind, offset). Returns count (>=0) or <0. */
 int btgpu_poll(btgpu_handle *h, btgpu_hit *out, int max_hits);
 /* Like btgpu_poll, plus what the reference hands to its packet handlers with every hit

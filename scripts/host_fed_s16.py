@@ -6,7 +6,9 @@ bench's capture quantised to int16 (peak 8000), fed once as float32 (the int16 v
 and once as int16 (4 bytes per sample, widened in the kernels).  Per format: Gsamples/s host-fed, the host-to-device copy of
 the same bytes alone, their ratio; and the device-resident step with the channel-bank and exact-rows kernel times
 (FLAG_TIMING_BANK).  Every figure is the median of --repeats timed regions of --batches batches after a warm-up, with the
-minimum and maximum beside it.  Prints one JSON line; --out writes it to a file as well."""
+minimum and maximum beside it.  Prints one JSON line; --out writes it to a file as well.
+--formats f32,s16,s8 picks the formats of this process (scripts/host_fed_formats.py runs one per process); with s8 among them the
+capture is quantised to int8 (peak 127) and EVERY format carries those values."""
 import argparse
 import hashlib
 import importlib
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--batches", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--formats", default="f32,s16")
+    ap.add_argument("--int8-values", action="store_true", help="quantise to peak 127 also when s8 is not among --formats")
     args = ap.parse_args()
     import torch
     from conftest import load_pkg
@@ -45,12 +49,15 @@ def main():
     b.close()
     seg, _ = synth.make_segment_torch(fs, fc, 0, S, "cuda", left_pad=H - 1 + mg, laps=laps, seed=1)
     f = torch.view_as_real(seg) if seg.is_complex() else seg.reshape(-1, 2)
-    q = torch.round(f * (8000.0 / f.abs().max())).to(torch.int16).contiguous()
+    names = args.formats.split(",")
+    peak = 127.0 if "s8" in names or args.int8_values else 8000.0
+    q = torch.round(f * (peak / f.abs().max())).to(torch.int16).contiguous()
     n = q.shape[0]
-    dev = {"f32": q.float().contiguous(), "s16": q}
+    dev = {"f32": q.float().contiguous(), "s16": q, "s8": q.to(torch.int8).contiguous()}
     res = {"workload": "c79", "slots_per_batch": S, "batches": hb, "repeats": args.repeats, "samples_per_batch": S * slot,
            "build_id": hashlib.sha256(open(os.path.join(ROOT, "gr-bluetooth_amd", "libbtgpu.so"), "rb").read()).hexdigest()[:16]}
-    for name, fmt in (("f32", pkg.FORMAT_F32), ("s16", pkg.FORMAT_S16)):
+    res["peak"] = peak
+    for name, fmt in ((nm, {"f32": pkg.FORMAT_F32, "s16": pkg.FORMAT_S16, "s8": getattr(pkg, "FORMAT_S8", None)}[nm]) for nm in names):
         pinned = dev[name].cpu().pin_memory()
         nbytes = pinned.numel() * pinned.element_size()
         # ---- host-fed ----
