@@ -35,9 +35,10 @@ FLAG_NO_VERIFY = 256      # polyphase path without the exact confirmation of its
 FLAG_EXACT_PAYLOAD = 512  # exported symbols exact to the end of the packet (include/btgpu.h)
 FLAG_EXACT_ALL = 1024     # no selection: every row of every channel exact (include/btgpu.h)
 FLAG_EXACT_DENSE = 2048   # exact rows in the dense form also where the sparse one exists (include/btgpu.h)
-EXACT_NONE, EXACT_SPARSE, EXACT_DENSE = 0, 1, 2     # exact_form()
+EXACT_NONE, EXACT_SPARSE, EXACT_DENSE, EXACT_NARROW = 0, 1, 2, 3     # exact_form()
 FLAG_DIRECT_MFMA = 4096  # the direct-form banks on the matrix pipe (include/btgpu.h)
 FLAG_PAYLOAD_SWEEP = 8192  # (implies HEADERS) crc_check under the 64 CLK1-6 candidates on the GPU; poll_payloads (include/btgpu.h)
+FLAG_EXACT_NARROW = 16384  # exact rows in the narrow form: eight channels as 16x16x4 matrix rows, decimation <= 8 (include/btgpu.h)
 DIRECT_VALU, DIRECT_MFMA = 0, 1                     # direct_form()
 KIND_AC, KIND_AA = 0, 1
 
@@ -524,7 +525,7 @@ class _MultiBlock:
         return t
 
     def exact_form(self):
-        """EXACT_NONE, EXACT_SPARSE or EXACT_DENSE: the form of the exact rows' kernel this block runs."""
+        """EXACT_NONE, EXACT_SPARSE, EXACT_DENSE or EXACT_NARROW: the form of the exact rows' kernel this block runs."""
         return self._L.btgpu_exact_form(self._h)
 
     def direct_form(self):

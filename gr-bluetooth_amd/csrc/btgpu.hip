@@ -123,6 +123,8 @@ struct btgpu_handle {
     DevBuf d_tapsA;                  // the direct-form channel bank's taps as exact_rows_kernel's A operand (exact_pack_taps)
     bool ex_dense = false;           // exact rows run in the dense form (exact_dense.hip.h): ex_kern / ex_kern_s16 are its kernels
     DevBuf d_tapsD;                  // ... and its A operand (exact_pack_taps_dense); allocated on those handles only
+    bool ex_narrow = false;          // exact rows run in the narrow form (exact_narrow.hip.h): its kernels in ex_kern*, its A operand
+                                     // (exact_pack_taps_narrow) in d_tapsD
     // the direct-form banks on the matrix pipe (ddc_mfma.hip.h; BTGPU_FLAG_DIRECT_MFMA / BTGPU_DIRECT_FORM=mfma): the channel bank
     // where the channelizer is DIRECT, the noise bank where the squelch is; their packed taps are allocated on those handles only
     bool direct_mfma = false;
@@ -521,7 +523,9 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
     auto launch_exact_rows = [&](const uint32_t *bitmap, unsigned int *stat, hipStream_t s_) {
         const ExactParams ep = make_exact_params(des, x_len, w0, G, (const float *)d_tapsA.p, (const float2 *)d_rot_ch.p, (const float *)d_atan.p,
                                                  bitmap, vb.bm_tiles, (float *)d_d.p, drow, (float *)(use_dcol ? t.d_dcol.p : nullptr), stat, (const float *)d_tapsD.p);
-        hipLaunchKernelGGL(fmt == kInS8 ? ex_kern_s8 : fmt == kInS16 ? ex_kern_s16 : ex_kern, dim3((unsigned)vb.bm_tiles), dim3(kExThreads), ex_lds, s_, ep, d_x);
+        // (the narrow form: row blocks on y, its workgroups stride over the tiles with their taps in registers)
+        const dim3 grid = ex_narrow ? dim3((unsigned)std::min(vb.bm_tiles, kEnGridX), (unsigned)exact_narrow_blocks(nch)) : dim3((unsigned)vb.bm_tiles);
+        hipLaunchKernelGGL(fmt == kInS8 ? ex_kern_s8 : fmt == kInS16 ? ex_kern_s16 : ex_kern, grid, dim3(kExThreads), ex_lds, s_, ep, d_x);
     };
     if (verify && exact_all) {
         hipLaunchKernelGGL(exact_mark_all_kernel, dim3((unsigned)((vb.bm_tiles * kExBmWords + 255) / 256)), dim3(256), 0, ps, vb.bm1, vb.bm_tiles, nch);
@@ -1110,6 +1114,8 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         if ((ch == BTGPU_CHANNELIZER_POLYPHASE && !pfb_ok) || (sq == BTGPU_SQUELCH_STAGED && !staged_ok) ||
             (ch != BTGPU_CHANNELIZER_POLYPHASE && ch != BTGPU_CHANNELIZER_DIRECT) ||
             (sq != BTGPU_SQUELCH_STAGED && sq != BTGPU_SQUELCH_DIRECT)) { delete h; return BTGPU_EUNSUPPORTED; }
+        // (the narrow exact rows rewrite the polyphase bank's stream: no such thing behind a channelizer that resolved to DIRECT)
+        if ((cfg->flags & BTGPU_FLAG_EXACT_NARROW) && ch != BTGPU_CHANNELIZER_POLYPHASE) { delete h; return BTGPU_EUNSUPPORTED; }
         h->use_pfb = ch == BTGPU_CHANNELIZER_POLYPHASE;
         h->pfb_small = h->use_pfb && !pfb100_ok;
         h->pfb_g = h->pfb_small && pfbg_runs;
@@ -1365,8 +1371,19 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
             const char *ef = getenv("BTGPU_EXACT_FORM");
             h->ex_dense = !h->ex_kern || (cfg->flags & BTGPU_FLAG_EXACT_DENSE) != 0 || (ef && std::strcmp(ef, "dense") == 0);
             if (ef && std::strcmp(ef, "sparse") == 0 && h->ex_kern) h->ex_dense = false;
+            // ... and narrow (exact_narrow.hip.h) on BTGPU_FLAG_EXACT_NARROW, and on BTGPU_EXACT_FORM=narrow where that form exists:
+            // D <= 8.  Never by default: profiles/exact_narrow_ab.json
+            const bool nflag = (cfg->flags & BTGPU_FLAG_EXACT_NARROW) != 0;
+            if (nflag && !exact_narrow_pick(d.decimation)) return fail(BTGPU_EUNSUPPORTED);
+            h->ex_narrow = nflag || (ef && std::strcmp(ef, "narrow") == 0 && exact_narrow_pick(d.decimation));
+            if (h->ex_narrow) h->ex_dense = false;
         }
-        if (h->ex_dense) {
+        if (h->ex_narrow) {
+            const std::vector<float> tn = exact_pack_taps_narrow(des.channel, d.decimation);
+            TRY(h->upload(h->d_tapsD, tn.data(), tn.size() * sizeof(float)));
+            h->ex_kern = exact_narrow_pick(d.decimation); h->ex_kern_s16 = exact_narrow_pick<kInS16>(d.decimation); h->ex_kern_s8 = exact_narrow_pick<kInS8>(d.decimation);
+            h->ex_lds = exact_narrow_lds_bytes(d.decimation);
+        } else if (h->ex_dense) {
             std::vector<float> td(exact_dense_taps_floats(nch, d.decimation));
             exact_pack_taps_dense(des.channel.taps.data(), nch, des.channel.ntp, d.decimation, td.data());
             TRY(h->upload(h->d_tapsD, td.data(), td.size() * sizeof(float)));
@@ -1781,7 +1798,7 @@ int btgpu_poll_payloads(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr, btgp
 int btgpu_exact_form(const btgpu_handle *h)
 {
     if (!h) return BTGPU_EINVAL;
-    return !h->verify ? BTGPU_EXACT_NONE : (h->ex_dense ? BTGPU_EXACT_DENSE : BTGPU_EXACT_SPARSE);
+    return !h->verify ? BTGPU_EXACT_NONE : (h->ex_narrow ? BTGPU_EXACT_NARROW : h->ex_dense ? BTGPU_EXACT_DENSE : BTGPU_EXACT_SPARSE);
 }
 
 int btgpu_direct_form(const btgpu_handle *h)

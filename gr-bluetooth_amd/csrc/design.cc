@@ -258,6 +258,8 @@ int make_design(const btgpu_config &cfg, Design &o)
 
     d.decimation = (int)d.samples_per_symbol / 2;
     if (d.decimation < 1) d.decimation = 1;
+    // the exact rows' narrow form (exact_narrow.hip.h) exists on the polyphase channelizer up to a decimation of 8
+    if ((cfg.flags & BTGPU_FLAG_EXACT_NARROW) && (d.decimation > 8 || cfg.channelizer == BTGPU_CHANNELIZER_DIRECT)) return BTGPU_EUNSUPPORTED;
     const double channel_sps = d.samples_per_symbol / d.decimation;
 
     // set_channels

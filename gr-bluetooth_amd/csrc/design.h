@@ -162,6 +162,14 @@ bool exact_rows_available(const Design &des);
 // past the last channel, and `ahead` * rb zero words of 1 KB behind the stream for its read-ahead.
 std::vector<float> pack_direct_mfma_taps(const FilterBank &b, int D, int rb, int ahead);
 
+// The A operand of exact_narrow_kernel (exact_narrow.hip.h: eight channels x (re, im) as the 16 rows of the 16x16x4 matrix
+// instruction), one float per lane and matrix instruction:
+//     [row block of 8 channels][tap block q of 14][instruction i of NI = ceil(2 D / 4)][lane of 64]
+// = row l & 15 = 2 (c % 8) + (re: 0, im: 1), K step l >> 4 of instruction i: the interleaved float f = 4 i + (l >> 4) of the tap
+// block, i.e. part e = f & 1 of tap j = q D + (f >> 1) -- exact_pack_taps' values, signs and swaps: (tr, -ti) along K for a re
+// row, (ti, tr) for an im row; zero in the K pad (f >= 2 D), beyond the filter and past the last channel.
+std::vector<float> exact_pack_taps_narrow(const FilterBank &b, int D);
+
 // direct-form bank builder shared by the reference-filter banks and the staged squelch
 void build_direct_bank(FilterBank &b, const std::vector<float> &h, int low_ch, int nch, double extra_hz,
                        double center_freq, double fs, int decim);

@@ -424,4 +424,20 @@ std::vector<float> pack_direct_mfma_taps(const FilterBank &b, int D, int rb, int
     return out;
 }
 
+std::vector<float> exact_pack_taps_narrow(const FilterBank &b, int D)
+{
+    const int NI = (2 * D + 3) / 4, NB = 14, nblk = (b.nch + 7) / 8;
+    std::vector<float> out((size_t)nblk * NB * NI * 64, 0.f);
+    for (int g = 0; g < nblk; g++)
+        for (int q = 0; q < NB; q++)
+            for (int i = 0; i < NI; i++)
+                for (int l = 0; l < 64; l++) {
+                    const int row = l & 15, f = 4 * i + (l >> 4), r = f >> 1, e = f & 1, c = 8 * g + (row >> 1), im = row & 1, j = q * D + r;
+                    float tr = 0.f, ti = 0.f;
+                    if (r < D && c < b.nch && j < b.ntp) { tr = b.taps[((size_t)c * b.ntp + j) * 2]; ti = b.taps[((size_t)c * b.ntp + j) * 2 + 1]; }
+                    out[(((size_t)g * NB + q) * NI + i) * 64 + l] = im ? (e ? tr : ti) : (e ? -ti : tr);
+                }
+    return out;
+}
+
 }  // namespace btgpu

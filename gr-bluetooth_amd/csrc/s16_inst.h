@@ -12,6 +12,7 @@
 #include "pfbg.hip.h"
 #include "exact.hip.h"
 #include "exact_dense.hip.h"
+#include "exact_narrow.hip.h"
 #include "ddc_mfma.hip.h"
 
 namespace btgpu {
@@ -59,6 +60,11 @@ BTGPU_S16_EX(50)
 #undef BTGPU_S16_EX
 // exact rows, dense form: one kernel for every decimation
 BTGPU_S16_KERNEL(exact_dense_kernel_s16<0>(ExactParams, const float2 *))
+// exact rows, narrow form: one kernel per number of matrix instructions in a tap block (D <= 8)
+BTGPU_S16_KERNEL(exact_narrow_kernel_s16<1>(ExactParams, const float2 *))
+BTGPU_S16_KERNEL(exact_narrow_kernel_s16<2>(ExactParams, const float2 *))
+BTGPU_S16_KERNEL(exact_narrow_kernel_s16<3>(ExactParams, const float2 *))
+BTGPU_S16_KERNEL(exact_narrow_kernel_s16<4>(ExactParams, const float2 *))
 // direct-form bank on the matrix pipe (BTGPU_FLAG_DIRECT_MFMA)
 BTGPU_S16_KERNEL(ddc_mfma_kernel_s16<0>(DdcMfmaParams))
 #undef BTGPU_S16_KERNEL

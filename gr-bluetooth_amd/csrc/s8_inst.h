@@ -12,6 +12,7 @@
 #include "pfbg.hip.h"
 #include "exact.hip.h"
 #include "exact_dense.hip.h"
+#include "exact_narrow.hip.h"
 #include "ddc_mfma.hip.h"
 
 namespace btgpu {
@@ -59,6 +60,11 @@ BTGPU_S8_EX(50)
 #undef BTGPU_S8_EX
 // exact rows, dense form: one kernel for every decimation
 BTGPU_S8_KERNEL(exact_dense_kernel_s8<0>(ExactParams, const float2 *))
+// exact rows, narrow form: one kernel per number of matrix instructions in a tap block (D <= 8)
+BTGPU_S8_KERNEL(exact_narrow_kernel_s8<1>(ExactParams, const float2 *))
+BTGPU_S8_KERNEL(exact_narrow_kernel_s8<2>(ExactParams, const float2 *))
+BTGPU_S8_KERNEL(exact_narrow_kernel_s8<3>(ExactParams, const float2 *))
+BTGPU_S8_KERNEL(exact_narrow_kernel_s8<4>(ExactParams, const float2 *))
 // direct-form bank on the matrix pipe (BTGPU_FLAG_DIRECT_MFMA)
 BTGPU_S8_KERNEL(ddc_mfma_kernel_s8<0>(DdcMfmaParams))
 #undef BTGPU_S8_KERNEL

@@ -114,6 +114,13 @@ extern "C" {
                                            mode only (multi_LAP has no packet handlers: BTGPU_EUNSUPPORTED from btgpu_design_query and
                                            btgpu_create).  Without the flag nothing of it is allocated or launched */
 
+#define BTGPU_FLAG_EXACT_NARROW 0x4000    /* exact rows in their NARROW form (csrc/exact_narrow.hip.h: eight channels x (re, im) as the 16 rows of
+                                           v_mfma_f32_16x16x4_f32, the row block's taps resident in registers).  The same bits in every row as
+                                           the other forms.  Exists on the polyphase channelizer with decimation <= 8 (the even rates
+                                           4 .. 16 Msps); with the flag at a higher rate or with a DIRECT channelizer btgpu_design_query and
+                                           btgpu_create return BTGPU_EUNSUPPORTED.  BTGPU_EXACT_FORM=narrow in the environment asks for it
+                                           where it exists and is ignored elsewhere (A/B timing: profiles/exact_narrow_ab.json) */
+
 #define BTGPU_KIND_AC 0
 #define BTGPU_KIND_AA 1
 
@@ -316,10 +323,11 @@ int btgpu_flush(btgpu_handle *h);
 
 int btgpu_last_timing(const btgpu_handle *h, btgpu_timing *out);
 
-/* Which form of the exact rows' kernel the handle runs (BTGPU_FLAG_EXACT_DENSE). */
+/* Which form of the exact rows' kernel the handle runs (BTGPU_FLAG_EXACT_DENSE, BTGPU_FLAG_EXACT_NARROW). */
 #define BTGPU_EXACT_NONE   0   /* no exact rows: DIRECT channelizer, or BTGPU_FLAG_NO_VERIFY */
 #define BTGPU_EXACT_SPARSE 1   /* exact_rows_kernel<D>: one (channel, tile) pair at a time    */
 #define BTGPU_EXACT_DENSE  2   /* exact_dense_kernel: channels as the matrix rows             */
+#define BTGPU_EXACT_NARROW 3   /* exact_narrow_kernel: eight channels as 16x16x4 matrix rows  */
 int btgpu_exact_form(const btgpu_handle *h);
 
 /* Which kernel the handle's direct-form banks run (BTGPU_FLAG_DIRECT_MFMA); VALU also where it has none. */

@@ -63,8 +63,75 @@ __global__ void mfma_chain_check(int steps, uint32_t seed, unsigned long long *m
     }
 }
 
+// The premise of exact_narrow.hip.h, `exact_mfma mfma16`: v_mfma_f32_16x16x4_f32 == the fmaf chain over k = 0, 1, 2, 3 of every step,
+// and v_mfma_f32_16x16x1_f32 (four blocks) == one chain step per instruction.  One wave = one 16 x 16 block (x4: four of them);
+// operand classes as above.  A: lane l = row l & 15, k = l >> 4 (x1: block l >> 4);  C/D: register e = row 4 (l >> 4) + e of
+// column l & 15 (x1: register 4 j + e = the same of block j).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__global__ void mfma16_chain_check(int steps, uint32_t seed, unsigned long long *mismatch, float *first_bad)
+{
+    const int lane = threadIdx.x & 63, col = lane & 15, kh = lane >> 4;
+    const uint32_t blk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6) + seed * 0x10001u;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < steps; s++) {
+        const int k = 4 * s + kh;
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(rnd_float(mix(blk, col, k)), rnd_float(mix(blk, 1000 + col, k)), acc, 0, 0, 0);
+    }
+    for (int e = 0; e < 4; e++) {
+        const int row = 4 * kh + e;
+        float ref = 0.f;
+        for (int k = 0; k < 4 * steps; k++) ref = fmaf(rnd_float(mix(blk, row, k)), rnd_float(mix(blk, 1000 + col, k)), ref);
+        if (__float_as_uint(ref) != __float_as_uint(acc[e])) {
+            if (atomicAdd(mismatch, 1ull) == 0) { first_bad[0] = ref; first_bad[1] = acc[e]; first_bad[2] = (float)row; first_bad[3] = (float)col; }
+        }
+    }
+}
+__global__ void mfma16x1_chain_check(int steps, uint32_t seed, unsigned long long *mismatch, float *first_bad)
+{
+    const int lane = threadIdx.x & 63, col = lane & 15, kh = lane >> 4;
+    const uint32_t blk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6) + seed * 0x10001u;
+    f32x16 acc;
+    for (int i = 0; i < 16; i++) acc[i] = 0.f;
+    for (int k = 0; k < steps; k++)                               // block j: A rows 16 j .. 16 j + 15, B columns 16 j .. 16 j + 15
+        acc = __builtin_amdgcn_mfma_f32_16x16x1f32(rnd_float(mix(blk, lane, k)), rnd_float(mix(blk, 1000 + lane, k)), acc, 0, 0, 0);
+    for (int i = 0; i < 16; i++) {
+        const int j = i >> 2, row = 16 * j + 4 * kh + (i & 3);
+        float ref = 0.f;
+        for (int k = 0; k < steps; k++) ref = fmaf(rnd_float(mix(blk, row, k)), rnd_float(mix(blk, 1000 + 16 * j + col, k)), ref);
+        if (__float_as_uint(ref) != __float_as_uint(acc[i])) {
+            if (atomicAdd(mismatch, 1ull) == 0) { first_bad[0] = ref; first_bad[1] = acc[i]; first_bad[2] = (float)row; first_bad[3] = (float)(16 * j + col); }
+        }
+    }
+}
+static int mfma16_main()
+{
+    unsigned long long *d_mis; float *d_bad;
+    CK(hipMalloc(&d_mis, 8)); CK(hipMalloc(&d_bad, 16));
+    const int blocks = 2560, waves = 4;
+    int rc = 0;
+    for (int form = 0; form < 2; form++) {
+        CK(hipMemset(d_mis, 0, 8)); CK(hipMemset(d_bad, 0, 16));
+        const int steps = form ? 100 : 25;                        // K = 100 either way
+        unsigned long long total = 0;
+        for (uint32_t seed = 1; seed <= 20; seed++) {
+            if (form) hipLaunchKernelGGL(mfma16x1_chain_check, dim3(blocks), dim3(64 * waves), 0, 0, steps, seed, d_mis, d_bad);
+            else hipLaunchKernelGGL(mfma16_chain_check, dim3(blocks), dim3(64 * waves), 0, 0, steps, seed, d_mis, d_bad);
+            total += (unsigned long long)blocks * waves * (form ? 1024 : 256) * 100;
+        }
+        CK(hipDeviceSynchronize());
+        unsigned long long mis; float bad[4];
+        CK(hipMemcpy(&mis, d_mis, 8, hipMemcpyDeviceToHost)); CK(hipMemcpy(bad, d_bad, 16, hipMemcpyDeviceToHost));
+        printf("%s vs fmaf chain over k ascending from +0 (K = 100): %llu products, %llu outputs differ", form ? "mfma_f32_16x16x1f32 (4 blocks)" : "mfma_f32_16x16x4f32", total, mis);
+        if (mis) printf(" (first: chain %a mfma %a at row %g col %g)", bad[0], bad[1], bad[2], bad[3]);
+        printf("\n");
+        if (mis) rc = 1;
+    }
+    return rc;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "mfma16")) return mfma16_main();
     const int per_tile = argc > 1 ? atoi(argv[1]) : 4;           // busy channels per tile in the timing run
     const int S = argc > 2 ? atoi(argv[2]) : 2304;               // slots of the timing run
     // ---- 1. MFMA == fmaf chain ----
