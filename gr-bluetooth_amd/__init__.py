@@ -39,6 +39,7 @@ EXACT_NONE, EXACT_SPARSE, EXACT_DENSE, EXACT_NARROW = 0, 1, 2, 3     # exact_for
 FLAG_DIRECT_MFMA = 4096  # the direct-form banks on the matrix pipe (include/btgpu.h)
 FLAG_PAYLOAD_SWEEP = 8192  # (implies HEADERS) crc_check under the 64 CLK1-6 candidates on the GPU; poll_payloads (include/btgpu.h)
 FLAG_EXACT_NARROW = 16384  # exact rows in the narrow form: eight channels as 16x16x4 matrix rows, decimation <= 8 (include/btgpu.h)
+FLAG_LE_SWEEP = 32768  # (implies SYMBOLS; needs FLAG_LE) CRC-24 and CRCInit of every access-address hit on the GPU; poll_le (include/btgpu.h)
 DIRECT_VALU, DIRECT_MFMA = 0, 1                     # direct_form()
 KIND_AC, KIND_AA = 0, 1
 
@@ -72,6 +73,12 @@ class Hit(ctypes.Structure):
         return (self.slot, self.channel, self.kind, self.offset, self.lap, self.ac_errors, self.nsym)
 
 
+class LeSweep(ctypes.Structure):
+    _fields_ = [("header", ctypes.c_uint16), ("verdict", ctypes.c_int16), ("length", ctypes.c_int32),
+                ("crc_rx", ctypes.c_uint32), ("crc_init", ctypes.c_uint32), ("match_len", ctypes.c_int16),
+                ("reserved", ctypes.c_int16)]
+
+
 K_DDC_CHANNEL, K_DEMOD_ENERGY, K_DDC_NOISE, K_NOISE_ENERGY, K_WINDOW = 0, 1, 2, 3, 4
 KERNEL_NAMES = ["ddc_channel", "demod_energy", "ddc_noise", "noise_energy", "window", "finish", "verify", "exact"]
 
@@ -93,7 +100,7 @@ EXPORTS = ["btgpu_design_query", "btgpu_acgen", "btgpu_filter_taps", "btgpu_stre
            "btgpu_debug_scan_symbols", "btgpu_debug_lut", "btgpu_process_host",
            "btgpu_work_s16", "btgpu_process_host_s16", "btgpu_process_device_s16",
            "btgpu_work_s8", "btgpu_process_host_s8", "btgpu_process_device_s8", "btgpu_exact_form", "btgpu_direct_form",
-           "btgpu_poll_payloads", "btgpu_debug_payload_sweep"]
+           "btgpu_poll_payloads", "btgpu_debug_payload_sweep", "btgpu_poll_le", "btgpu_debug_le_sweep", "btgpu_poll_records"]
 
 
 class BtgpuError(RuntimeError):
@@ -193,6 +200,12 @@ def lib():
     L.btgpu_debug_payload_sweep.restype = ctypes.c_long
     L.btgpu_debug_payload_sweep.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_void_p, ctypes.c_void_p]
+    L.btgpu_poll_le.restype = ctypes.c_int
+    L.btgpu_poll_le.argtypes = [vp, ctypes.POINTER(Hit), ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
+                                ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    L.btgpu_debug_le_sweep.restype = ctypes.c_long
+    L.btgpu_debug_le_sweep.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_void_p]
     L.btgpu_hopseq_create.restype = ctypes.c_int
     L.btgpu_hopseq_create.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     L.btgpu_hopseq_destroy.restype = None
@@ -321,6 +334,29 @@ def debug_payload_sweep(packets, to_header=72, device=-1):
     if got < 0:
         raise BtgpuError(int(got), "btgpu_debug_payload_sweep")
     return hdrs, crcs
+
+
+LE_SWEEP_DTYPE = np.dtype([("header", "<u2"), ("verdict", "<i2"), ("length", "<i4"), ("crc_rx", "<u4"), ("crc_init", "<u4"),
+                           ("match_len", "<i2"), ("reserved", "<i2")])
+
+
+def debug_le_sweep(packets, le_index, device=-1):
+    """le_sweep_kernel straight on captured packets (btgpu_debug_le_sweep): `packets` is a list of symbol arrays (0/1 per
+    symbol) that start at the preamble, `le_index` the LE channel index (0 .. 39) of each.  Returns [n] of LE_SWEEP_DTYPE."""
+    n = len(packets)
+    lens = np.array([len(p) for p in packets], np.int32)
+    idx = np.ascontiguousarray(le_index, np.int32)
+    if idx.shape != (n,):
+        raise ValueError("one LE index per packet")
+    stride = max(int(lens.max()) if n else 0, 1)
+    buf = np.zeros((n, stride), np.uint8)
+    for i, p in enumerate(packets):
+        buf[i, :lens[i]] = np.asarray(p, np.uint8) & 1
+    out = np.zeros(n, LE_SWEEP_DTYPE)
+    got = lib().btgpu_debug_le_sweep(buf.ctypes.data, lens.ctypes.data, idx.ctypes.data, n, stride, device, out.ctypes.data)
+    if got < 0:
+        raise BtgpuError(int(got), "btgpu_debug_le_sweep")
+    return out
 
 
 def staged_design(sample_rate, center_freq):
@@ -518,6 +554,24 @@ class _MultiBlock:
         if got < 0:
             raise BtgpuError(got, "btgpu_poll_payloads")
         return hits[:got], hdrs[:got], crcs[:got], syms[:got], lens[:got]
+
+    LE_SWEEP_DTYPE = LE_SWEEP_DTYPE
+
+    def poll_le(self, sym_cap=3125, max_hits=1 << 16):
+        """poll_symbols plus, per hit, the LE sweep -- dewhitened PDU header, CRC-24 verdict, CRCInit, first matching length
+        (needs flags=FLAG_LE | FLAG_LE_SWEEP): (hits, sweeps [n] of LE_SWEEP_DTYPE, symbols, lens)."""
+        n = min(max(self._L.btgpu_pending(self._h), 0), max_hits)
+        hits = np.zeros(max(n, 1), self.HIT_DTYPE)
+        les = np.zeros(max(n, 1), self.LE_SWEEP_DTYPE)
+        syms = np.zeros((max(n, 1), sym_cap), np.uint8)
+        lens = np.zeros(max(n, 1), np.int32)
+        # (asked even where nothing is pending: a handle without the flag answers BTGPU_EUNSUPPORTED)
+        got = self._L.btgpu_poll_le(self._h, hits.ctypes.data_as(ctypes.POINTER(Hit)), les.ctypes.data,
+                                    syms.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), sym_cap,
+                                    lens.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n)
+        if got < 0:
+            raise BtgpuError(got, "btgpu_poll_le")
+        return hits[:got], les[:got], syms[:got], lens[:got]
 
     def timing(self):
         t = Timing()

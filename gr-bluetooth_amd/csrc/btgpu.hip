@@ -17,6 +17,7 @@
 #include "design.h"
 #include "kernels.hip.h"
 #include "payload_sweep.hip.h"
+#include "le_sweep.hip.h"
 #include "pfb100.hip.h"
 #include "s16_inst.h"        // the int16-input kernels: declared here, compiled in s16_kernels.hip
 #include "s8_inst.h"         // the int8-input kernels: declared here, compiled in s8_kernels.hip
@@ -83,6 +84,7 @@ struct btgpu_handle {
     struct TailCtx {                 // per in-flight batch: everything the front writes and the post / tail stages read
         DevBuf d_winlen, d_hits, d_hitcount, d_fin, d_winfin, d_symbits, d_hdr;
         DevBuf d_crc;                         // payload sweeps of the batch's hits (BTGPU_FLAG_PAYLOAD_SWEEP: payload_sweep_kernel)
+        DevBuf d_le;                          // LE sweeps of the batch's hits (BTGPU_FLAG_LE_SWEEP: le_sweep_kernel)
         DevBuf d_d;                           // demodulated stream of the batch, time-major [G][drow] -- not allocated where d_dcol is the stream
         DevBuf d_dcol;                        // 100-bin bank: the stream tile by tile channel-major [tile][80][25], the only one of such a handle
         DevBuf d_ptile, d_phead;              // polyphase banks: |Y|^2 tile sums (-> block_sum_kernel on the post stream)
@@ -94,6 +96,7 @@ struct btgpu_handle {
         DevBuf d_eon, d_eoff, d_snr;          // E_on, E_off, SNR per window (window_kernel, or squelch_kernel when the squelch is deferred)   // exact confirmation (verify.hip.h): task list, exact rows, task stream
         HeaderRec *h_hdr = nullptr;           // pinned: sweeps of the first eager_hdr hits (records_out_kernel)
         PayloadRec *h_crc = nullptr;          // pinned: payload sweeps of the first eager_hdr hits (payload_out_kernel)
+        LeRec *h_le = nullptr;                // pinned: LE sweeps of the first eager_hdr hits (le_out_kernel)
         uint32_t *h_sym = nullptr;            // pinned: packed symbols of the first eager_fin hit windows (records_out_kernel)
         unsigned int *h_count = nullptr;      // pinned: {hits, finish records, -, -, verify tasks, verify tiles, turned away, -}
         DeviceHit *h_hits = nullptr;          // pinned: first eager_hits records (records_out_kernel)
@@ -137,7 +140,7 @@ struct btgpu_handle {
     // not an asynchronous copy: with three batches queued the call came back only when the device had drained -- 26 ms per five
     // batches at C8 (11 068 hit windows per batch, 2876 beyond the eager copy): the pipeline emptied every fifth call, 7.2 ms per
     // step for 4.0 ms of kernels (profiles/r06_q_c8_*)
-    void *h_spill[4] = {nullptr, nullptr, nullptr, nullptr}; size_t h_spill_cap[4] = {0, 0, 0, 0};     // hits | symbols | headers | payload sweeps
+    void *h_spill[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t h_spill_cap[5] = {0, 0, 0, 0, 0};     // hits | symbols | headers | payload sweeps | LE sweeps
     void *spill_buf(int k, size_t bytes)
     {
         if (bytes <= h_spill_cap[k]) return h_spill[k];
@@ -155,6 +158,8 @@ struct btgpu_handle {
     // The host queue: records of harvested batches in emission order, consumed from the front (qhead).  Flat arenas -- a record
     // costs one memcpy of its symbols, no allocation (a vector per record was 5 ms of host time per 11 000-record batch at C8:
     // twice the batch's kernels, profiles/r06_q_c8_*).
+    bool want_le = false;                        // BTGPU_FLAG_LE_SWEEP: le_sweep_kernel behind the header sweep
+    std::vector<btgpu_le_sweep> qle;             // LE sweep per queued hit (BTGPU_FLAG_LE_SWEEP)
     std::vector<btgpu_header> qhdr;              // header sweep per queued hit (BTGPU_FLAG_HEADERS)
     std::vector<btgpu_crc_sweep> qcrc;           // payload sweep per queued hit (BTGPU_FLAG_PAYLOAD_SWEEP)
     std::vector<uint32_t> qbits;                 // packed symbols per queued hit [n][kSymWords] (BTGPU_FLAG_SYMBOLS)
@@ -164,11 +169,12 @@ struct btgpu_handle {
     void pop_records(size_t n)
     {
         qhead += n;
-        if (qhead == queue.size()) { queue.clear(); qhdr.clear(); qcrc.clear(); qbits.clear(); qhas.clear(); qhead = 0; }
+        if (qhead == queue.size()) { queue.clear(); qhdr.clear(); qcrc.clear(); qle.clear(); qbits.clear(); qhas.clear(); qhead = 0; }
         else if (qhead >= 8192 && 2 * qhead >= queue.size()) {                     // (amortised: at most one move per record)
             queue.erase(queue.begin(), queue.begin() + qhead);
             if (want_hdrs) qhdr.erase(qhdr.begin(), qhdr.begin() + qhead);
             if (want_crc) qcrc.erase(qcrc.begin(), qcrc.begin() + qhead);
+            if (want_le) qle.erase(qle.begin(), qle.begin() + qhead);
             if (want_syms) { qbits.erase(qbits.begin(), qbits.begin() + qhead * kSymWords); qhas.erase(qhas.begin(), qhas.begin() + qhead); }
             qhead = 0;
         }
@@ -242,10 +248,11 @@ struct btgpu_handle {
                          &d_pfb_taps_n, &d_binpos_n, &d_krot_n, &d_h3, &d_w, &d_taps_s1, &d_rot_s1, &d_rotstep_s1, &d_prof, &d_pcol, &d_wh18, &d_tapsA, &d_tapsD, &d_tapsM_ch, &d_tapsM_n};
         for (DevBuf *b : all) if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
         for (TailCtx &t : tc) {
-            DevBuf *tb[] = {&t.d_winlen, &t.d_hits, &t.d_hitcount, &t.d_fin, &t.d_winfin, &t.d_symbits, &t.d_hdr, &t.d_crc, &t.d_d, &t.d_dcol,
+            DevBuf *tb[] = {&t.d_winlen, &t.d_hits, &t.d_hitcount, &t.d_fin, &t.d_winfin, &t.d_symbits, &t.d_hdr, &t.d_crc, &t.d_le, &t.d_d, &t.d_dcol,
                             &t.d_ptile, &t.d_phead, &t.d_pfine, &t.d_Z, &t.d_vtasks, &t.d_vcount, &t.d_dxt, &t.d_winbits_v, &t.d_bm, &t.d_chanfloor, &t.d_eon, &t.d_eoff, &t.d_snr};
             if (t.h_hdr) { (void)hipHostFree(t.h_hdr); t.h_hdr = nullptr; }
             if (t.h_crc) { (void)hipHostFree(t.h_crc); t.h_crc = nullptr; }
+            if (t.h_le) { (void)hipHostFree(t.h_le); t.h_le = nullptr; }
             if (t.h_sym) { (void)hipHostFree(t.h_sym); t.h_sym = nullptr; }
             for (DevBuf *b : tb) if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
             for (auto &e : t.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -253,7 +260,7 @@ struct btgpu_handle {
             if (t.h_count) { (void)hipHostFree(t.h_count); t.h_count = nullptr; }
             if (t.h_hits) { (void)hipHostFree(t.h_hits); t.h_hits = nullptr; }
         }
-        for (int k = 0; k < 4; k++) if (h_spill[k]) { (void)hipHostFree(h_spill[k]); h_spill[k] = nullptr; h_spill_cap[k] = 0; }
+        for (int k = 0; k < 5; k++) if (h_spill[k]) { (void)hipHostFree(h_spill[k]); h_spill[k] = nullptr; h_spill_cap[k] = 0; }
         for (int k = 0; k < 2; k++) {
             if (h_stage[k]) { (void)hipHostFree(h_stage[k]); h_stage[k] = nullptr; }
             if (ev_copied[k]) { (void)hipEventDestroy(ev_copied[k]); ev_copied[k] = nullptr; }
@@ -675,6 +682,10 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
                                        (const HeaderRec *)t.d_hdr.p, dd.correlator == BTGPU_CORRELATOR_BTBB ? 68 : 72,
                                        (PayloadRec *)t.d_crc.p);
             }
+            if (want_le)
+                hipLaunchKernelGGL(le_sweep_kernel, dim3(1024), dim3(64), 0, tail_stream, (const DeviceHit *)d_hits.p,
+                                   (const unsigned int *)d_hitcount.p, max_hits, (const uint32_t *)d_symbits.p,
+                                   (const int8_t *)d_le_index.p, des.d.low_channel, (LeRec *)t.d_le.p);
             // records travel to page-locked host memory on the tail stream too -- through a kernel that knows the counts (the
             // first eager_fin hit windows' symbols, eager_hdr sweeps, eager_hits records; beyond: harvest's spill copies) --
             // harvesting a batch is then pure host work and never waits on the other streams
@@ -686,6 +697,9 @@ int btgpu_handle::process_batch(const float2 *d_x, size_t x_len, long long w0, u
             if (want_crc)
                 hipLaunchKernelGGL(payload_out_kernel, dim3(64), dim3(256), 0, tail_stream, (const unsigned int *)d_hitcount.p, max_hits,
                                    (const uint2 *)t.d_crc.p, (uint2 *)t.h_crc, eager_hdr);
+            if (want_le)
+                hipLaunchKernelGGL(le_out_kernel, dim3(64), dim3(256), 0, tail_stream, (const unsigned int *)d_hitcount.p, max_hits,
+                                   (const uint32_t *)t.d_le.p, (uint32_t *)t.h_le, eager_hdr);
         }
     }
     HIPCHK(this, mark(10, tail_stream));
@@ -834,6 +848,8 @@ int btgpu_handle::harvest(TailCtx &t)
         const size_t n_crc_spill = want_crc ? n_hdr_spill : 0;
         const DeviceHit *hit_spill = nullptr; const uint32_t *sym_spill = nullptr; const HeaderRec *hdr_spill = nullptr;
         const PayloadRec *crc_spill = nullptr;
+        const size_t n_le_spill = (want_le && count > eager_hdr) ? (size_t)(count - eager_hdr) : 0;
+        const LeRec *le_spill = nullptr;
         if (n_hit_spill) {
             void *b = spill_buf(0, n_hit_spill * sizeof(DeviceHit));
             if (!b) { set_error("hipHostMalloc (record spill)"); return BTGPU_ENOMEM; }
@@ -858,7 +874,13 @@ int btgpu_handle::harvest(TailCtx &t)
             HIPCHK(this, hipMemcpyAsync(b, (const PayloadRec *)t.d_crc.p + eager_hdr, n_crc_spill * sizeof(PayloadRec), hipMemcpyDeviceToHost, spill_stream));
             crc_spill = (const PayloadRec *)b;
         }
-        if (n_hit_spill || n_sym_spill || n_hdr_spill) HIPCHK(this, hipStreamSynchronize(spill_stream));
+        if (n_le_spill) {
+            void *b = spill_buf(4, n_le_spill * sizeof(LeRec));
+            if (!b) { set_error("hipHostMalloc (LE sweep spill)"); return BTGPU_ENOMEM; }
+            HIPCHK(this, hipMemcpyAsync(b, (const LeRec *)t.d_le.p + eager_hdr, n_le_spill * sizeof(LeRec), hipMemcpyDeviceToHost, spill_stream));
+            le_spill = (const LeRec *)b;
+        }
+        if (n_hit_spill || n_sym_spill || n_hdr_spill || n_le_spill) HIPCHK(this, hipStreamSynchronize(spill_stream));
         auto hit_at = [&](size_t i) -> const DeviceHit & { return i < eager_hits ? t.h_hits[i] : hit_spill[i - eager_hits]; };
         // the order the reference's loops print in -- slot, channel, kind, offset -- formed FIRST, on packed keys; the records then go
         // to the queue's arenas in that order, once
@@ -877,6 +899,7 @@ int btgpu_handle::harvest(TailCtx &t)
         if (want_syms) { qbits.resize((q0 + n) * kSymWords); qhas.resize(q0 + n); }
         if (want_hdrs) qhdr.resize(q0 + n);
         if (want_crc) qcrc.resize(q0 + n);
+        if (want_le) qle.resize(q0 + n);
         for (size_t k = 0; k < n; k++) {
             const size_t hit_index = order[k].second;
             const DeviceHit &x = hit_at(hit_index);
@@ -909,6 +932,10 @@ int btgpu_handle::harvest(TailCtx &t)
                 static_assert(sizeof(btgpu_crc_sweep) == sizeof(PayloadRec), "the record is the ABI's");
                 std::memcpy(&qcrc[q0 + k], hit_index < eager_hdr ? &t.h_crc[hit_index] : &crc_spill[hit_index - eager_hdr], sizeof(PayloadRec));
                 qcrc[q0 + k].reserved = 0;
+            }
+            if (want_le) {
+                static_assert(sizeof(btgpu_le_sweep) == sizeof(LeRec), "the record is the ABI's");
+                std::memcpy(&qle[q0 + k], hit_index < eager_hdr ? &t.h_le[hit_index] : &le_spill[hit_index - eager_hdr], sizeof(LeRec));
             }
         }
     }
@@ -1258,7 +1285,8 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
                   getenv("BTGPU_DEFER") && atoi(getenv("BTGPU_DEFER")) == 1;
     h->want_crc = (cfg->flags & BTGPU_FLAG_PAYLOAD_SWEEP) != 0;
     h->want_hdrs = (cfg->flags & BTGPU_FLAG_HEADERS) != 0 || h->want_crc;
-    h->want_syms = (cfg->flags & BTGPU_FLAG_SYMBOLS) != 0 || h->want_hdrs;
+    h->want_le = (cfg->flags & BTGPU_FLAG_LE_SWEEP) != 0;
+    h->want_syms = (cfg->flags & BTGPU_FLAG_SYMBOLS) != 0 || h->want_hdrs || h->want_le;
     h->exact_all = h->verify && (cfg->flags & BTGPU_FLAG_EXACT_ALL) != 0;
     // (BTGPU_FLAG_EXACT_PAYLOAD: accepted, and always on since round 6 -- a packet's air time is busy, so its rows are exact to its end)
 
@@ -1460,6 +1488,7 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         if (h->use_dcol) TRY(h->alloc(t.d_dcol, (size_t)((h->ystride + 64) / (kBankNT - 1) + 2) * 80 * (kBankNT - 1) * sizeof(float)));
         if (h->want_hdrs) TRY(h->alloc(t.d_hdr, (size_t)h->max_hits * sizeof(HeaderRec)));
         if (h->want_crc) TRY(h->alloc(t.d_crc, (size_t)h->max_hits * sizeof(PayloadRec)));
+        if (h->want_le) TRY(h->alloc(t.d_le, (size_t)h->max_hits * sizeof(LeRec)));
         if (h->want_syms) {
             const size_t maxfin = (size_t)S * nch;            // one FinishRec per hit window, whatever max_hits is
             TRY(h->alloc(t.d_winfin, (size_t)S * nch * sizeof(int)));
@@ -1478,6 +1507,7 @@ int btgpu_create(const btgpu_config *cfg, btgpu_handle **out)
         }
         if (h->want_hdrs && hipHostMalloc((void **)&t.h_hdr, (size_t)h->eager_hdr * sizeof(HeaderRec), hipHostMallocDefault) != hipSuccess) return fail(BTGPU_ENOMEM);
         if (h->want_crc && hipHostMalloc((void **)&t.h_crc, (size_t)h->eager_hdr * sizeof(PayloadRec), hipHostMallocDefault) != hipSuccess) return fail(BTGPU_ENOMEM);
+        if (h->want_le && hipHostMalloc((void **)&t.h_le, (size_t)h->eager_hdr * sizeof(LeRec), hipHostMallocDefault) != hipSuccess) return fail(BTGPU_ENOMEM);
         if (h->want_syms && hipHostMalloc((void **)&t.h_sym, (size_t)h->eager_fin * kSymWords * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return fail(BTGPU_ENOMEM);
         if (hipHostMalloc((void **)&t.h_count, 12 * sizeof(unsigned int), hipHostMallocDefault) != hipSuccess) return fail(BTGPU_ENOMEM);
         std::memset(t.h_count, 0, 12 * sizeof(unsigned int));
@@ -1749,10 +1779,10 @@ int btgpu_poll(btgpu_handle *h, btgpu_hit *out, int max_hits)
 }
 
 static int poll_symbols_impl(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr, uint8_t *symbols, int sym_cap, int *sym_len,
-                             int max_hits, btgpu_crc_sweep *crc = nullptr)
+                             int max_hits, btgpu_crc_sweep *crc = nullptr, btgpu_le_sweep *le = nullptr)
 {
     if (!h || (!out && max_hits > 0) || max_hits < 0 || sym_cap < 0 || (!symbols && sym_cap > 0)) return BTGPU_EINVAL;
-    if (!h->want_syms || (hdr && !h->want_hdrs) || (crc && !h->want_crc)) return BTGPU_EUNSUPPORTED;
+    if (!h->want_syms || (hdr && !h->want_hdrs) || (crc && !h->want_crc) || (le && !h->want_le)) return BTGPU_EUNSUPPORTED;
     (void)h->harvest_all(false);
     int n = (int)std::min<size_t>((size_t)max_hits, h->pending_records());
     for (int i = 0; i < n; i++) {
@@ -1760,6 +1790,7 @@ static int poll_symbols_impl(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr,
         out[i] = h->queue[qi];
         if (hdr) hdr[i] = h->qhdr[qi];
         if (crc) crc[i] = h->qcrc[qi];
+        if (le) le[i] = h->qle[qi];
         const uint32_t *bits = &h->qbits[qi * kSymWords];
         // what the reference hands to ac()/aa(): &symp[i], len - i  (one symbol per byte, air order)
         int avail = h->qhas[qi] ? out[i].nsym : 0;
@@ -1793,6 +1824,19 @@ int btgpu_poll_payloads(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr, btgp
     if ((!hdr || !crc) && max_hits > 0) return BTGPU_EINVAL;
     if (h && !h->want_crc) return BTGPU_EUNSUPPORTED;
     return poll_symbols_impl(h, out, hdr, symbols, sym_cap, sym_len, max_hits, crc);
+}
+
+int btgpu_poll_le(btgpu_handle *h, btgpu_hit *out, btgpu_le_sweep *le, uint8_t *symbols, int sym_cap, int *sym_len, int max_hits)
+{
+    if (!le && max_hits > 0) return BTGPU_EINVAL;
+    if (h && !h->want_le) return BTGPU_EUNSUPPORTED;
+    return poll_symbols_impl(h, out, nullptr, symbols, sym_cap, sym_len, max_hits, nullptr, le);
+}
+
+int btgpu_poll_records(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr, btgpu_crc_sweep *crc, btgpu_le_sweep *le, uint8_t *symbols,
+                       int sym_cap, int *sym_len, int max_hits)
+{
+    return poll_symbols_impl(h, out, hdr, symbols, sym_cap, sym_len, max_hits, crc, le);
 }
 
 int btgpu_exact_form(const btgpu_handle *h)
@@ -1999,6 +2043,56 @@ long btgpu_debug_payload_sweep(const uint8_t *symbols, const int32_t *lengths, i
         static_assert(sizeof(btgpu_header) == sizeof(HeaderRec) && sizeof(btgpu_crc_sweep) == sizeof(PayloadRec), "the records are the ABI's");
         if (hipMemcpy(hdr, d_hdr, np * sizeof(HeaderRec), hipMemcpyDeviceToHost) != hipSuccess) break;
         if (hipMemcpy(crc, d_crc, np * sizeof(PayloadRec), hipMemcpyDeviceToHost) != hipSuccess) break;
+        result = (long)np;
+    } while (0);
+    cleanup();
+    return result;
+}
+
+// The LE sweep on captured packets (parity entry): le_sweep_kernel as the tail of a batch launches it, on records built here --
+// offset 0, one packed row per packet, the channel number standing for the LE index through an identity table
+long btgpu_debug_le_sweep(const uint8_t *symbols, const int32_t *lengths, const int32_t *le_index, int n_packets, int stride,
+                          int device, btgpu_le_sweep *out)
+{
+    if (!symbols || !lengths || !le_index || !out || n_packets < 0 || stride <= 0) return BTGPU_EINVAL;
+    for (int i = 0; i < n_packets; i++)
+        if (lengths[i] < 0 || lengths[i] > stride || lengths[i] > 32 * kSymWords || le_index[i] < 0 || le_index[i] > 39) return BTGPU_EINVAL;
+    if (n_packets == 0) return 0;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return BTGPU_ENODEVICE;
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    if (device >= ndev || hipSetDevice(device) != hipSuccess) return BTGPU_EINVAL;
+    const size_t np = (size_t)n_packets;
+    std::vector<uint32_t> rows(np * kSymWords, 0u);
+    std::vector<DeviceHit> hh(np);
+    for (size_t i = 0; i < np; i++) {
+        const uint8_t *s = symbols + i * (size_t)stride;
+        for (int k = 0; k < lengths[i]; k++) if (s[k] & 1) rows[i * kSymWords + (k >> 5)] |= 1u << (k & 31);
+        DeviceHit h{};
+        h.slot = (uint32_t)i; h.channel_idx = le_index[i]; h.kind = 1; h.nsym = lengths[i]; h.sym = (int32_t)i;
+        hh[i] = h;
+    }
+    int8_t ident[79];
+    for (int k = 0; k < 79; k++) ident[k] = (int8_t)(k < 40 ? k : -1);
+    const unsigned int count = (unsigned int)np;
+    uint32_t *d_rows = nullptr; DeviceHit *d_hits = nullptr; unsigned int *d_count = nullptr; int8_t *d_ident = nullptr; LeRec *d_le = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_rows); (void)hipFree(d_hits); (void)hipFree(d_count); (void)hipFree(d_ident); (void)hipFree(d_le); };
+    if (hipMalloc((void **)&d_rows, rows.size() * 4) != hipSuccess || hipMalloc((void **)&d_hits, np * sizeof(DeviceHit)) != hipSuccess ||
+        hipMalloc((void **)&d_count, sizeof(unsigned int)) != hipSuccess || hipMalloc((void **)&d_ident, sizeof ident) != hipSuccess ||
+        hipMalloc((void **)&d_le, np * sizeof(LeRec)) != hipSuccess) {
+        (void)hipGetLastError(); cleanup(); return BTGPU_ENOMEM;
+    }
+    long result = BTGPU_EDEVICE;
+    do {
+        if (hipMemcpy(d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(d_hits, hh.data(), np * sizeof(DeviceHit), hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(d_count, &count, sizeof count, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(d_ident, ident, sizeof ident, hipMemcpyHostToDevice) != hipSuccess) break;
+        hipLaunchKernelGGL(le_sweep_kernel, dim3(std::min(count, 1024u)), dim3(64), 0, 0, (const DeviceHit *)d_hits, (const unsigned int *)d_count,
+                           n_packets, (const uint32_t *)d_rows, (const int8_t *)d_ident, 0, d_le);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
+        static_assert(sizeof(btgpu_le_sweep) == sizeof(LeRec), "the record is the ABI's");
+        if (hipMemcpy(out, d_le, np * sizeof(LeRec), hipMemcpyDeviceToHost) != hipSuccess) break;
         result = (long)np;
     } while (0);
     cleanup();

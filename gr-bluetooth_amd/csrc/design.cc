@@ -241,6 +241,7 @@ int make_design(const btgpu_config &cfg, Design &o)
     if (corr != BTGPU_CORRELATOR_INTREE && corr != BTGPU_CORRELATOR_BTBB) return BTGPU_EINVAL;
     if (corr == BTGPU_CORRELATOR_BTBB && cfg.mode != BTGPU_MODE_LAP) return BTGPU_EUNSUPPORTED;   // multi_sniffer uses sniff_ac
     if ((cfg.flags & BTGPU_FLAG_PAYLOAD_SWEEP) && cfg.mode != BTGPU_MODE_SNIFFER) return BTGPU_EUNSUPPORTED;   // multi_LAP decodes no packets
+    if ((cfg.flags & BTGPU_FLAG_LE_SWEEP) && (cfg.mode != BTGPU_MODE_SNIFFER || !(cfg.flags & BTGPU_FLAG_LE))) return BTGPU_EUNSUPPORTED;   // no access-address records to sweep
     o.cfg = cfg;
     btgpu_design &d = o.d;
     std::memset(&d, 0, sizeof d);

@@ -37,6 +37,10 @@ multi_block::multi_block(double sample_rate, double center_freq, double squelch_
     const char *ps = getenv("BTGPU_PAYLOAD_SWEEP");
     d_payloads = d_headers && ps && atoi(ps) == 1;
     if (d_payloads) flags |= BTGPU_FLAG_PAYLOAD_SWEEP;
+    // CRC-24 and CRCInit of every access-address hit (csrc/le_sweep.hip.h): off unless the environment asks
+    const char *ls = getenv("BTGPU_LE_SWEEP");
+    d_le_sweep = d_headers && (flags & BTGPU_FLAG_LE) && ls && atoi(ls) == 1;
+    if (d_le_sweep) flags |= BTGPU_FLAG_LE_SWEEP;
     d_sample_rate = sample_rate;
     d_center_freq = center_freq;
     d_target_snr = squelch_threshold;
@@ -107,15 +111,20 @@ void multi_block::drain(btgpu_handle *g)
         std::vector<int> lens(buf.size());
         std::vector<btgpu_header> hdrs(buf.size());
         std::vector<btgpu_crc_sweep> crcs(d_payloads ? buf.size() : 0);
+        std::vector<btgpu_le_sweep> les(d_le_sweep ? buf.size() : 0);
         for (;;) {
-            int n = d_payloads ? btgpu_poll_payloads(g, buf.data(), hdrs.data(), crcs.data(), syms.data(), cap, lens.data(), (int)buf.size())
+            int n = d_le_sweep ? btgpu_poll_records(g, buf.data(), hdrs.data(), d_payloads ? crcs.data() : nullptr, les.data(), syms.data(), cap,
+                                                    lens.data(), (int)buf.size())
+                  : d_payloads ? btgpu_poll_payloads(g, buf.data(), hdrs.data(), crcs.data(), syms.data(), cap, lens.data(), (int)buf.size())
                                : btgpu_poll_headers(g, buf.data(), hdrs.data(), syms.data(), cap, lens.data(), (int)buf.size());
             if (n <= 0) break;
             for (int i = 0; i < n; i++) {
                 d_crc_now = d_payloads && buf[i].kind == BTGPU_KIND_AC ? &crcs[i] : nullptr;
+                d_le_now = d_le_sweep && buf[i].kind == BTGPU_KIND_AA ? &les[i] : nullptr;
                 handle_hit(buf[i], &hdrs[i], syms.data() + (size_t)i * cap, buf[i].kind == BTGPU_KIND_AC ? lens[i] : std::min(lens[i], 3125));
             }
             d_crc_now = nullptr;
+            d_le_now = nullptr;
         }
     } else {
         for (;;) {
@@ -253,6 +262,8 @@ protected:
             // aa() (lib/multi_sniffer_impl.cc:207-226): "time %6d, snr=%.1f, " + le_packet::print()
             printf("time %6d, snr=%.1f, ", (int)(h.slot & 0x7ffffff), h.snr_db);
             fputs(host::le_packet_text(syms, nsyms, h.channel).c_str(), stdout);
+            if (d_le_now && d_le_now->verdict >= 0)
+                printf("  CRC=%06x %s, CRCInit=%06x\n", d_le_now->crc_rx, d_le_now->verdict ? "ok" : "bad", d_le_now->crc_init);
             return;
         }
         // ac() and everything it calls (lib/multi_sniffer_impl.cc:169-365): the "time ..." prefix,

@@ -31,6 +31,8 @@ protected:
     bool d_headers = false;               // records come with symbols and the header sweep
     bool d_payloads = false;              // ... and the payload sweep (BTGPU_PAYLOAD_SWEEP=1 in the environment)
     const btgpu_crc_sweep *d_crc_now = nullptr;   // the payload sweep of the record handle_hit is looking at (or null)
+    bool d_le_sweep = false;              // ... and the LE sweep (BTGPU_LE_SWEEP=1 in the environment)
+    const btgpu_le_sweep *d_le_now = nullptr;     // the LE sweep of the record handle_hit is looking at (or null)
     bool d_warned_turned_away = false;    // the "second run's list was full" warning has been printed
 
     // forwards one scheduler call to btgpu_work(); returns the number of items consumed

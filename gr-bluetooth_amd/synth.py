@@ -92,13 +92,28 @@ def le_whitening_bits(le_index, n):
     return np.array(out, dtype=np.uint8)
 
 
-def le_advert_bits(le_index, rng, payload_bytes=12, pdu_type=0, aa=0x8E89BED6):
-    """Air-order bits of an LE advertising-channel packet: preamble, access address, whitened
-    (PDU header, payload); CRC bits are random (nothing on the hot path checks them)."""
+def le_crc24(bits, init=0x555555):
+    """The 24 CRC bits, in air order, of the PDU `bits` (air order, before whitening): Core Vol 6 Part B 3.1.1,
+    x^24 + x^10 + x^9 + x^6 + x^4 + x^3 + x + 1, position 0 of the register = LSB of `init`, sent from position 23 down."""
+    reg = [(init >> i) & 1 for i in range(24)]
+    for b in bits:
+        fb = reg[23] ^ int(b)
+        reg = [fb] + reg[:23]
+        for t in (1, 3, 4, 6, 9, 10):
+            reg[t] ^= fb
+    return np.array(reg[::-1], dtype=np.uint8)
+
+
+def le_advert_bits(le_index, rng, payload_bytes=12, pdu_type=0, aa=0x8E89BED6, crc=False, crc_init=0x555555):
+    """Air-order bits of an LE packet: preamble, access address, whitened (PDU header, payload, CRC).  The CRC bits are
+    random unless crc=True (the default keeps every capture built so far bit for bit); then they are le_crc24 under
+    `crc_init` (0x555555 on the advertising channels, a connection's CRCInit on the data channels)."""
     aab = [(aa >> i) & 1 for i in range(32)]
     pre = [0, 1, 0, 1, 0, 1, 0, 1] if aab[0] == 0 else [1, 0, 1, 0, 1, 0, 1, 0]
     hdr = [(pdu_type >> i) & 1 for i in range(8)] + [(payload_bytes >> i) & 1 for i in range(8)]
     body = np.array(hdr + list(rng.integers(0, 2, 8 * payload_bytes + 24)), dtype=np.uint8)
+    if crc:
+        body[-24:] = le_crc24(body[:-24], crc_init)
     body ^= le_whitening_bits(le_index, len(body))
     return np.concatenate([np.array(pre + aab, dtype=np.uint8), body])
 

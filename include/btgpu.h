@@ -121,6 +121,12 @@ extern "C" {
                                            btgpu_create return BTGPU_EUNSUPPORTED.  BTGPU_EXACT_FORM=narrow in the environment asks for it
                                            where it exists and is ignored elsewhere (A/B timing: profiles/exact_narrow_ab.json) */
 
+#define BTGPU_FLAG_LE_SWEEP 0x8000        /* (implies SYMBOLS; needs BTGPU_FLAG_LE, sniffer mode) behind every access-address hit, on the GPU
+                                           (csrc/le_sweep.hip.h): the dewhitened PDU header, the CRC-24 at the header's length and at every
+                                           other payload length, and the CRCInit the packet implies; btgpu_poll_le.  Without BTGPU_FLAG_LE or
+                                           in BTGPU_MODE_LAP: BTGPU_EUNSUPPORTED from btgpu_design_query and btgpu_create.  Without the flag
+                                           nothing of it is allocated or launched */
+
 #define BTGPU_KIND_AC 0
 #define BTGPU_KIND_AA 1
 
@@ -317,6 +323,33 @@ typedef struct btgpu_crc_sweep {
 /* btgpu_poll_headers plus the payload sweep of each record; needs BTGPU_FLAG_PAYLOAD_SWEEP (BTGPU_EUNSUPPORTED without) */
 int btgpu_poll_payloads(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr, btgpu_crc_sweep *crc, uint8_t *symbols, int sym_cap,
                         int *sym_len, int max_hits);
+/* What lies behind an access-address hit (csrc/le_sweep.hip.h).  The PDU is the symbols from hit.offset + 40 on, symbols the record
+ * does not have read as 0, dewhitened with the channel's sequence.  header: its first 16 bits, host order; the length field is
+ * header >> 8, all eight bits (Core 4.2+).  verdict: 1 the advertising-init (0x555555) CRC-24 over the 2 + len bytes equals the 24
+ * symbols that follow, 0 it does not, -1 not computed (kind AC, or fewer than 8 (2 + len + 3) symbols behind the access address).
+ * crc_rx: those 24 symbols as the CRC register holds them when it is shifted out (first symbol = bit 0).  crc_init: the init under
+ * which the CRC at the header's length holds -- 0x555555 on a good advertising packet, the connection's CRCInit on a data-channel
+ * packet; 0xFFFFFFFF where the verdict is -1.  match_len: the smallest payload length L in 0 .. 255 at which the advertising-init
+ * CRC of the PDU as it would be at that length -- 2 + L bytes, the header's length byte reading L -- equals the 24 symbols behind
+ * it, all of them present; -1 = none.  It is the header's length on a good packet, and the packet's length where the length field
+ * itself took the bit error (the CRC covers the header, so the CRC of the PDU as received holds at no length then).  length as in
+ * btgpu_crc_sweep.  Records of kind AC are zero with
+ * verdict -1, crc_init 0xFFFFFFFF and match_len -1. */
+typedef struct btgpu_le_sweep {
+    uint16_t header;
+    int16_t  verdict;
+    int32_t  length;
+    uint32_t crc_rx;
+    uint32_t crc_init;
+    int16_t  match_len;
+    int16_t  reserved;
+} btgpu_le_sweep;
+/* btgpu_poll_symbols plus the LE sweep of each record; needs BTGPU_FLAG_LE_SWEEP (BTGPU_EUNSUPPORTED without) */
+int btgpu_poll_le(btgpu_handle *h, btgpu_hit *out, btgpu_le_sweep *le, uint8_t *symbols, int sym_cap, int *sym_len, int max_hits);
+/* btgpu_poll_symbols plus whichever sweeps the caller names (hdr, crc, le: each may be null): for a consumer that wants the classic
+ * sweeps and the LE sweep of one record stream.  BTGPU_EUNSUPPORTED where a named sweep's flag is off */
+int btgpu_poll_records(btgpu_handle *h, btgpu_hit *out, btgpu_header *hdr, btgpu_crc_sweep *crc, btgpu_le_sweep *le, uint8_t *symbols,
+                       int sym_cap, int *sym_len, int max_hits);
 int btgpu_pending(const btgpu_handle *h);
 /* Wait for every enqueued batch and move its records to the poll queue (BTGPU_FLAG_ASYNC). */
 int btgpu_flush(btgpu_handle *h);
@@ -367,6 +400,13 @@ long btgpu_debug_scan_symbols(const uint8_t *symbols, size_t n, int device, int 
  * (offset 0, nsym = lengths[i]) and returns both records per packet.  Returns n_packets or a negative error.  No handle needed. */
 long btgpu_debug_payload_sweep(const uint8_t *symbols, const int32_t *lengths, int n_packets, int stride, int device, int to_header,
                                btgpu_header *hdr, btgpu_crc_sweep *crc);
+
+/* ---- parity entry: the LE sweep on captured packets ----
+ * Packet i at symbols[i * stride], one symbol per byte (0/1), from the preamble on (the offset sniff_aa returns), lengths[i]
+ * (<= stride, <= 3840) symbols, LE channel index le_index[i] in 0 .. 39.  Runs le_sweep_kernel on them as the tail of a batch does
+ * (offset 0, nsym = lengths[i]).  Returns n_packets or a negative error.  No handle needed. */
+long btgpu_debug_le_sweep(const uint8_t *symbols, const int32_t *lengths, const int32_t *le_index, int n_packets, int stride,
+                          int device, btgpu_le_sweep *out);
 
 /* ---- hop reversal: the piconet's complete hopping sequence on the GPU ----
  * Replaces basic_rate_piconet_impl::init_hop_reversal's precalc + address_precalc + gen_hops
